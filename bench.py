@@ -81,6 +81,11 @@ def parse():
                          '--size, --batch 32 by default; reports images/sec and achieved GB/s of the decode / NMS kernels')
     ap.add_argument('--no-infer-leg', action='store_true',
                     help='skip the configs[1] inference leg that the default N = 1 run attaches as `inference` after the timed region')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, '
+                         '< 64 MB in all; a fixed, seeded sample of the larger arrays) so that two builds can be compared output '
+                         'for output: training step -> loss, the three heads\' output / pred, the parameter gradients; --infer -> '
+                         'the decoded predictions and the detections')
     ap.add_argument('--stub-step', action='store_true',
                     help='TEST ONLY (tests/test_host_logic.py): a CPU / gloo stand-in for the step, to exercise the launcher, '
                          'barrier and max-over-ranks plumbing without a GPU; the line it prints is marked "stub": true and is not a measurement')
@@ -338,6 +343,30 @@ def pmc_recorded(kind, sym):
     return None, None
 
 
+DUMP_SAMPLE = 1 << 20              # elements kept of one head tensor / of the predictions (4 MB each)
+DUMP_GRAD_SAMPLE = 1 << 22         # elements kept of the 64.9 M parameter gradients (16 MB)
+
+
+def dump_sample(t, n, seed):
+    """t flattened in logical (NCHW) order as float32 on the host: all of it if it has at most n elements, else the n
+    elements at fixed positions drawn without replacement from `seed` (the same positions for the same shape)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), n, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> float32 / float64 ndarray, written as path/<name>.npy"""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f'--dump-outputs: {total} bytes'
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 _ARGS = {}
 
 
@@ -390,7 +419,7 @@ def cpu_baseline(size, batch):
                       f'torch threads {threads}, host cpus {os.cpu_count()}'}
 
 
-def infer_leg(args, steps=None, warmup=None):
+def infer_leg(args, steps=None, warmup=None, dump=None):
     """BASELINE configs[1]: 1xMI355X inference, 608x608 bs=32 (val.py path: eval forward -> postprocess).  One JSON line:
     images/sec of forward + postprocess, and for the HBM-bound head kernels the achieved GB/s against their algorithmic
     bytes (decode reads + writes B*N*85*4 B = 15.47 MB/img; the candidate count reads it once more), measured
@@ -438,7 +467,9 @@ def infer_leg(args, steps=None, warmup=None):
             out = m(x)
         sc = (out[..., 4:5] * out[..., 5:]).flatten()
         # confidence threshold giving ~500 candidates per image (survivors 1e2..1e3 per image)
-        thr = float(torch.quantile(sc[torch.randint(0, sc.numel(), (1000000,), device=dev)], 1 - 500.0 / (out.shape[1] * 80)))
+        # (positions from a generator of its own: the threshold is an input of the timed path, the same from run to run)
+        pick = torch.randint(0, sc.numel(), (1000000,), device=dev, generator=torch.Generator(device=dev).manual_seed(79))
+        thr = float(torch.quantile(sc[pick], 1 - 500.0 / (out.shape[1] * 80)))
         U.postprocess(out.clone(), 80, thr, 0.4)
         rec.clear()
         torch.cuda.synchronize()
@@ -454,6 +485,11 @@ def infer_leg(args, steps=None, warmup=None):
             tf += b_ - a
             tp += time.perf_counter() - b_
         dt = time.perf_counter() - t0
+    if dump:
+        # predictions as postprocess leaves them (box columns rewritten to corners); detections [n, 1 + 7], image index first
+        rows = [torch.cat([torch.full((len(d), 1), float(b), device=d.device), d.float()], 1) for b, d in enumerate(det) if d is not None]
+        dump_outputs(dump, {'predictions': dump_sample(out, DUMP_SAMPLE, 1),
+                            'detections': torch.cat(rows).cpu().numpy() if rows else np.zeros((0, 8), np.float32)})
     N = out.shape[1]
     ms = lambda key: sum(e0.elapsed_time(e1) for e0, e1 in rec[key]) / steps
     dec_bytes = 2.0 * B * N * 85 * 4
@@ -500,7 +536,7 @@ def main():
         return stub_main(args)
     if args.infer:
         quiet = _QuietStdout()
-        return quiet.emit(json.dumps(infer_leg(args)))
+        return quiet.emit(json.dumps(infer_leg(args, dump=args.dump_outputs)))
     quiet = _QuietStdout()
     rank = int(os.environ.get('RANK', 0))
     local = int(os.environ.get('LOCAL_RANK', 0))
@@ -551,7 +587,9 @@ def main():
 
     from yolov4_amd import trace
 
-    def step():
+    heads = []                                           # --dump-outputs: the head outputs of the last timed step
+
+    def step(keep=False):
         ddp.zero_grad()
         with trace.range('y4.forward'):                  # roctx ranges with Y4_ROCTX=1 (no-ops otherwise)
             out_ = ddp(x)
@@ -559,6 +597,8 @@ def main():
             loss = crit(out_, {'padded_labels': labels})
         with trace.range('y4.backward'):
             loss.backward()                              # the exchange is waited for by BucketedDDP's end-of-backward callback
+        if keep:
+            heads[:] = out_
         return loss
 
     for _ in range(args.warmup):
@@ -573,8 +613,8 @@ def main():
     fence()
     timer.on = True
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=bool(args.dump_outputs) and i == args.steps - 1)
     fence()
     dt = time.perf_counter() - t0
     timer.on = False
@@ -583,6 +623,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     lossv = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the step holds after it: the loss, the head outputs (after the loss's in-place masking) and the
+        # parameter gradients (all-reduced), the latter concatenated in named_parameters() order
+        grads = torch.cat([p.grad.reshape(-1) for _, p in model.named_parameters()])
+        arrays = {'loss': np.array(lossv, np.float64),
+                  'grads': dump_sample(grads, DUMP_GRAD_SAMPLE, 2)}
+        del grads
+        for od in heads:
+            for k in ('output', 'pred'):
+                arrays[f"head{od['layer_no']}_{k}"] = dump_sample(od[k], DUMP_SAMPLE, 10 + od['layer_no'])
+        dump_outputs(args.dump_outputs, arrays)
+    heads.clear()
 
     if rank == 0:
         ms = dt / args.steps * 1e3

@@ -204,23 +204,46 @@ def recipe_sd(golden):
     return sd
 
 
+def _double(sd):
+    return {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+
+
+# The fixtures are fp32 results of the reference on the machine that made them.  On this random-weight, ill-conditioned net
+# the rounding of fp32 arithmetic -- which the CPU's thread count and vector ISA reorder -- moves results by more than the
+# fixed tolerances below, so each bound is the larger of that tolerance and 4 e32 (2 e32 for a norm), e32 = how far the
+# oracle's own fp32 result is from its fp64 evaluation of the same graph on this machine (the bound of
+# tests/test_gpu_configs.py::test_training_step_on_maps_with_odd_sizes_vs_the_oracle).
+
+
 def test_model_eval_forward(golden, recipe_sd):
     g = golden('model')
+    x_cal, x = recipe.randn((8, 3, 64, 64), 77), recipe.randn((2, 3, 64, 64), 78)
+    net64 = NW.RefNet(_double(recipe_sd), CFG)
+    net64.calibrate(x_cal.double())
     net = NW.RefNet(recipe_sd, CFG)
-    net.calibrate(recipe.randn((8, 3, 64, 64), 77))
+    net.calibrate(x_cal)
     for k in g.files:
         if k.startswith('cal.'):
-            close(net.p[k[4:]].numpy(), g[k], 1e-4, 1e-3)
-    out = net.forward_eval(recipe.randn((2, 3, 64, 64), 78))
+            e32 = float((net.p[k[4:]].double() - net64.p[k[4:]]).abs().max())
+            close(net.p[k[4:]].numpy(), g[k], max(1e-4, 4 * e32), 1e-3)
+    out = net.forward_eval(x)
+    with torch.no_grad():                                    # fp64 graph, decoded in fp32 as the reference's YOLOLayer does
+        lg64 = net64.logits(x.double())
+    out64 = np.concatenate([H.yolo_decode(t.float().numpy(), l, CFG, False) for l, t in enumerate(lg64)], 1)
+    e_sc = float(np.abs(out[..., 4:] - out64[..., 4:]).max())
+    e_box = float(np.abs(out[..., :4] - out64[..., :4]).max())
     ref = g['eval64.out']
-    close(out[..., 4:], ref[..., 4:], 1e-4, 1e-4)            # obj / cls: abs 1e-4
-    close(out[..., :4], ref[..., :4], 1e-3, 1e-4)            # boxes (px, values up to hundreds): rel 1e-4
+    close(out[..., 4:], ref[..., 4:], max(1e-4, 4 * e_sc), 1e-4)     # obj / cls: abs 1e-4
+    close(out[..., :4], ref[..., :4], max(1e-3, 4 * e_box), 1e-4)    # boxes (px, values up to hundreds): rel 1e-4
     det = H.postprocess(out.copy(), 80, 0.12, 0.4)
     for b in range(2):
         rd = g[f'eval64.det{b}']
         assert det[b].shape == rd.shape
         assert np.array_equal(det[b][:, 6], rd[:, 6])        # same classes in the same order
-        close(det[b], rd, 1e-3, 1e-4)
+        # the same boxes per class: two survivors of one class whose scores are closer than the rounding may trade places
+        d, r = (a[np.lexsort((a[:, 0], a[:, 6]))] for a in (det[b], rd))
+        close(d[:, :4], r[:, :4], max(1e-3, 4 * e_box), 1e-4)    # corners: differences of two box columns
+        close(d[:, 4:], r[:, 4:], max(1e-3, 4 * e_sc), 1e-4)
 
 
 def test_model_train_step(golden, recipe_sd):
@@ -228,19 +251,28 @@ def test_model_train_step(golden, recipe_sd):
     net = NW.RefNet(recipe_sd, CFG)
     x = recipe.randn((2, 3, 128, 128), 80)
     labels = recipe.synth_labels(2, 128, 81, counts=[9, 21])
+    net64 = NW.RefNet(_double(recipe_sd), CFG)
     loss, lg = net.train_step(x, labels.numpy())
     assert abs(loss - float(g['train128.loss'])) <= 1e-4 * float(g['train128.loss'])
     for l in range(3):
         out, pred = H.yolo_decode(lg[l].detach().numpy(), l, CFG, True)
         close(out, g[f'train128.output{l}'], 1e-4, 1e-4)
         close(pred, g[f'train128.pred{l}'], 1e-3, 1e-4)
+    # the fp64 backward of the same graph from the same loss gradient
+    _, G = H.yolo_loss([t.detach().numpy() for t in lg], labels.numpy(), CFG, 0.7)
+    torch.autograd.backward(net64.forward_train(x.double()), [torch.from_numpy(t).double() for t in G])
+
+    def e32(k):
+        t64 = net64.p[k].grad
+        return float((net.p[k].grad.double() - t64).norm() / t64.norm())
     keys = [str(q) for q in g['train128.gradnorm_keys']]
     for kk, ref in zip(keys, g['train128.gradnorm']):
         got = float(net.p[kk].grad.double().norm())
-        assert abs(got - ref) <= 2e-3 * max(ref, 1e-6), (kk, got, ref)
+        # two fp32 norms differ by at most the norm of their difference: ~ 2 e32 (this machine's and the fixture's rounding)
+        assert abs(got - ref) <= max(2e-3, 2 * e32(kk)) * max(ref, 1e-6), (kk, got, ref, e32(kk))
     for k in g.files:
         if k.startswith('train128.grad.'):
             ref = g[k]
-            close(net.p[k[14:]].grad.numpy(), ref, 1e-3 * float(np.abs(ref).max()), 1e-3)
+            close(net.p[k[14:]].grad.numpy(), ref, max(1e-3, 4 * e32(k[14:])) * float(np.abs(ref).max()), 1e-3)
         if k.startswith('train128.after.'):
             close(net.p[k[15:]].numpy(), g[k], 1e-5, 1e-4)
