@@ -56,7 +56,7 @@ __device__ __forceinline__ float y4_act(float x, int act) {
     switch (act) {
         case Y4_ACT_LEAKY: return x > 0.0f ? x : 0.1f * x;
         case Y4_ACT_MISH: return y4_mish(x);
-        case Y4_ACT_RELU: return fmaxf(x, 0.0f);
+        case Y4_ACT_RELU: return x < 0.0f ? 0.0f : x;      // (not fmaxf: a NaN stays a NaN, as in torch)
         default: return x;
     }
 }
@@ -73,7 +73,7 @@ __device__ __forceinline__ float y4_act_grad(float x, int act) {
 template <int ACT> __device__ __forceinline__ float y4_act_t(float x) {
     if constexpr (ACT == Y4_ACT_LEAKY) return x > 0.0f ? x : 0.1f * x;
     else if constexpr (ACT == Y4_ACT_MISH) return y4_mish(x);
-    else if constexpr (ACT == Y4_ACT_RELU) return fmaxf(x, 0.0f);
+    else if constexpr (ACT == Y4_ACT_RELU) return x < 0.0f ? 0.0f : x;
     else return x;
 }
 template <int ACT> __device__ __forceinline__ float y4_act_grad_t(float x) {

@@ -1041,15 +1041,15 @@ int y4_bn_act_fwd_f32(const float* y, int ldy, const float* mean, const float* i
     // in whole 32-channel tiles, i.e. z 128-B aligned)
     if (z_planes && ((!out_amax && z_planes != 3) || (C & 31))) return Y4_ERR_SHAPE;
     if (z_planes && !planes_twin && ldz != C && (ldz < C || (ldz & 31) || (reinterpret_cast<uintptr_t>(z) & 127))) return Y4_ERR_SHAPE;
-    if (z_planes == 2) {
-        // the scale comes from an analytic bound of max|z| (no measuring pass); a residual must bring its own maximum
-        if (residual && !res_amax) return Y4_ERR_NULL;
+    // the scale of z_planes == 2 comes from an analytic bound of max|z| (no measuring pass); a residual must bring its own maximum
+    if (z_planes == 2 && residual && !res_amax) return Y4_ERR_NULL;
+    if (!vec_ok(y, ldy, C) || (z && !vec_ok(z, ldz, C)) || (residual && !vec_ok(residual, ldr, C)) || M <= 0)
+        return Y4_ERR_SHAPE;
+    if (z_planes == 2) {                                   // after every check: a refused call leaves *out_amax as it was
         hipLaunchKernelGGL(bn_planes_bound_kernel, dim3(1), dim3(256), 0, y4_stream(stream), gamma, beta, C,
                            sqrtf((float)(M > 1 ? M - 1 : 1)), residual ? res_amax : nullptr, out_amax);
         Y4_CHECK_LAUNCH();
     }
-    if (!vec_ok(y, ldy, C) || (z && !vec_ok(z, ldz, C)) || (residual && !vec_ok(residual, ldr, C)) || M <= 0)
-        return Y4_ERR_SHAPE;
     const RowMap rm = row_map(C);
     long long blocks = (M + rm.rpb * PW_UNROLL - 1) / (rm.rpb * PW_UNROLL);
     if (blocks > 256 * 16) blocks = 256 * 16;
