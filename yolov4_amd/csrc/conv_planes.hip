@@ -1012,6 +1012,7 @@ static bool stream_bf16_ok(const PlaneConvGeom& g, bool dst_bf16) {
     static const bool off = getenv("Y4_BF_STREAM") && atoi(getenv("Y4_BF_STREAM")) == 0;
     if (off || g.k != 1 || g.stride != 1 || (g.Cs != 64 && g.Cs != 128) || g.N > 128 || g.N < 1) return false;
     if (dst_bf16 && (g.res || (g.N & 1))) return false;
+    if (g.res && g.ldr == 0) return false;                 // a bias (one row for every pixel): the tile kernel's epilogue has that window
     return g.M >= 128 * 1024;
 }
 template <bool YB>
