@@ -467,6 +467,43 @@ int y4_sgd_multi_step_f32(const void* chunks_dev, int nchunks, const float* hype
 int y4_preprocess_u8_f32(const void* src, int src_h, int src_w, long long src_pitch_bytes, int swap_rb,
                          float* dst, long long dst_sc, long long dst_sh, long long dst_sw, int S, void* stream);
 
+/* ---------------------------------------------------------------- ImageNet classifier (backbone pre-training)
+ * The four operations behind the backbone in CSPDarknet53 (darknet/darknet.py:164-193) and its training script
+ * (darknet/main_amp.py:184 CrossEntropyLoss(label_smoothing=0.1), :549-562 accuracy).  fp32 throughout; outputs are
+ * overwritten, never accumulated; every floating-point reduction runs in a fixed order (bit-identical run to run, no float
+ * atomics); element k of a row lies at row * ld + k and columns >= the logical width are never written.
+ *
+ * nn.AdaptiveAvgPool2d((1, 1)): x is [B][HW] pixel rows of pitch ldx >= C, y is [B] rows of pitch ldy >= C;
+ * y[b][c] = (sum_p x[b][p][c]) / HW; backward dx[b][p][c] = dy[b][c] / HW.  B <= 65535 in the forward call (a grid dimension). */
+int y4_avgpool_global_fwd_f32(const float* x, int ldx, float* y, int ldy, int B, int HW, int C, void* stream);
+int y4_avgpool_global_bwd_f32(const float* dy, int lddy, float* dx, int lddx, int B, int HW, int C, void* stream);
+/* nn.Linear: y[m][n] = sum_k x[m][k] w[n][k] + bias[n]; w is dense [N][K] (the layout of nn.Linear.weight), bias may be
+ * NULL.  fp32 products, fp32 accumulation in k order (no reduced-precision split).  Backward: dx = dy w [M][K] (pitch lddx),
+ * dw = dy^T x [N][K] dense, dbias = sum_m dy; each output is skipped when NULL (all three NULL: Y4_ERR_NULL), x is only read
+ * for dw and w only for dx.  No output is split over its reduction index, so there is nothing to combine.  M, K, N <= 65535 * 64. */
+int y4_linear_fwd_f32(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy, int M, int K, int N,
+                      void* stream);
+int y4_linear_bwd_f32(const float* x, int ldx, const float* w, const float* dy, int lddy, float* dx, int lddx, float* dw,
+                      float* dbias, int M, int K, int N, void* stream);
+/* torch.nn.CrossEntropyLoss(label_smoothing = smoothing), ignore_index -100, mean reduction, on logits [B][N] (pitch ldl)
+ * and int64 labels target[B]:  row_loss[b] = lse_b - (1 - smoothing) z_t - smoothing mean_j z_j  with a max-subtracted lse;
+ * rows labelled -100 give 0 and are not counted.  loss_out (2 doubles) = {sum of the counted rows / their number, that
+ * number}, reduced in double; the mean is NaN when nothing is counted, as in torch.  A label is only ever compared with the
+ * column index, never used in an address: a label outside [0, N) other than -100 reads nothing out of bounds and makes its
+ * row, and with it the mean, NaN.
+ * Backward: dlogits[b][j] = gscale[0] / counted * (softmax_j - (1 - smoothing) [j == t] - smoothing / N), exactly 0 in
+ * ignored rows; gscale is a device float (the upstream gradient), loss_out is what the forward call wrote (only the count
+ * is read); the row statistics are recomputed from the logits. */
+int y4_ce_smooth_fwd_f32(const float* logits, int ldl, const long long* target, int B, int N, double smoothing,
+                         float* row_loss /* [B] */, double* loss_out /* [2] */, void* stream);
+int y4_ce_smooth_bwd_f32(const float* logits, int ldl, const long long* target, const double* loss_out, const float* gscale,
+                         float* dlogits, int lddl, int B, int N, double smoothing, void* stream);
+/* accuracy(): rank_b = #{j: z_j > z_t} + #{j < t: z_j == z_t} (ties go to the lower index; torch leaves their order open),
+ * rank_b = N for a row that holds a NaN or whose label is outside [0, N) (-100 included);
+ * correct[i] = #{b: rank_b < ks_host[i]} for the nk (1..8) values of k (k > N is allowed); rank (int32 [B]) may be NULL. */
+int y4_topk_correct_f32(const float* logits, int ldl, const long long* target, int B, int N, const int* ks_host, int nk,
+                        int* correct /* [nk] */, int* rank /* [B] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@ Drop-in for the hot-path modules of zjykzj/YOLOv4:
 
     reference import                              this package
     darknet.darknet.ConvBNAct / ResBlock / ...    yolov4_amd.darknet.darknet
+    darknet.darknet.CSPDarknet53 / Backbone       yolov4_amd.darknet.darknet (+ .loss, .train: main_amp.py's pieces)
     yolo.model.yolov4.YOLOv4                      yolov4_amd.yolo.model.yolov4
     yolo.model.yololayer.YOLOLayer                yolov4_amd.yolo.model.yololayer
     yolo.model.yololoss.YOLOLoss                  yolov4_amd.yolo.model.yololoss

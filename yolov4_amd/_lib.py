@@ -100,6 +100,13 @@ PROTOTYPES = {
     'y4_adam_multi_step_f32': (I, [P, I, P, I, F, F, F, F, P]),
     'y4_sgd_multi_step_f32': (I, [P, I, P, I, F, P]),
     'y4_preprocess_u8_f32': (I, [P, I, I, L, I, P, L, L, L, I, P]),
+    'y4_avgpool_global_fwd_f32': (I, [P, I, P, I, I, I, I, P]),
+    'y4_avgpool_global_bwd_f32': (I, [P, I, P, I, I, I, I, P]),
+    'y4_linear_fwd_f32': (I, [P, I, P, P, P, I, I, I, I, P]),
+    'y4_linear_bwd_f32': (I, [P, I, P, P, I, P, I, P, P, I, I, I, P]),
+    'y4_ce_smooth_fwd_f32': (I, [P, I, P, I, I, c_double, P, P, P]),
+    'y4_ce_smooth_bwd_f32': (I, [P, I, P, P, P, P, I, I, I, c_double, P]),
+    'y4_topk_correct_f32': (I, [P, I, P, I, I, P, I, P, P, P]),
 }
 
 _lib = None

@@ -333,3 +333,11 @@ class CSPDownSample(nn.Module):
         x2 = blk(self.part2[0](xb, out_planes=first, dx_put=fb), out_planes=last)
         x2 = self.part2[2](x2, out=cb.slot(0))
         return self.transition(ops.cat([x2, x1], into=cb), out_planes=soft(plan_for(readers, xa.shape[2:], xa.shape[0]), self) if readers else False)
+
+
+def __getattr__(name):
+    """Backbone / CSPDarknet53 (darknet.py:141-193) live in .classifier, which imports this module: resolved on first use."""
+    if name in ('Backbone', 'CSPDarknet53'):
+        from . import classifier
+        return getattr(classifier, name)
+    raise AttributeError(f'module {__name__!r} has no attribute {name!r}')

@@ -1620,3 +1620,133 @@ def yolo_loss_dense_targets(last):
     check(L.y4_yolo_loss_dense_targets_f32(_ptr(target), _ptr(tgt_mask), _ptr(tgt_scale), B, F, A, K, C,
                                            _ptr(last['ws']), last['nbytes'], _stream()), 'yolo_loss_dense_targets')
     return target, tgt_mask, tgt_scale
+
+
+# ------------------------------------------------------------------ ImageNet classifier (csrc/classifier.hip)
+def _rows(t, what):
+    """(tensor, row pitch) of a 2-D fp32 device tensor whose rows are contiguous; repacks any other layout."""
+    _require_gpu(t, what)
+    if t.dim() != 2:
+        raise Y4Error(f'{what}: expected a 2-D tensor, got {tuple(t.shape)}')
+    if t.shape[1] > 1 and t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]))
+
+
+def _labels(target, B, device, what):
+    if target.dim() != 1 or target.shape[0] != B or target.dtype != torch.int64:
+        raise Y4Error(f'{what}: target must be int64 [{B}], got {target.dtype} {tuple(target.shape)}')
+    return target.detach().to(device).contiguous()
+
+
+class AvgPoolGlobalFn(torch.autograd.Function):
+    """nn.AdaptiveAvgPool2d((1, 1)), darknet/darknet.py:169,189: [B,C,H,W] -> [B,C,1,1]."""
+
+    @staticmethod
+    def forward(ctx, x):
+        L = lib()
+        _require_gpu(x, 'avgpool input')
+        if x.dim() != 4:
+            raise Y4Error(f'avgpool input: expected [B,C,H,W], got {tuple(x.shape)}')
+        B, C, H, W = x.shape
+        x, ldx = as_nhwc(x, need_vec4=False)
+        y = torch.empty((B, C, 1, 1), device=x.device, dtype=torch.float32)
+        check(L.y4_avgpool_global_fwd_f32(_ptr(x), ldx, _ptr(y), C, B, H * W, C, _stream()), 'avgpool_fwd')
+        ctx.shape = (B, C, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        L = lib()
+        B, C, H, W = ctx.shape
+        g = g.reshape(B, C).contiguous()
+        dx = empty_nhwc(B, C, H, W, g.device)
+        check(L.y4_avgpool_global_bwd_f32(_ptr(g), C, _ptr(dx), nhwc_pitch(dx), B, H * W, C, _stream()), 'avgpool_bwd')
+        return dx
+
+
+class LinearFn(torch.autograd.Function):
+    """nn.Linear on [M,K] rows, darknet/darknet.py:170,192."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        L = lib()
+        x, ldx = _rows(x, 'linear input')
+        _require_gpu(w, 'linear weight')
+        if w.dim() != 2 or w.shape[1] != x.shape[1] or (bias is not None and tuple(bias.shape) != (w.shape[0],)):
+            raise Y4Error(f'linear: input {tuple(x.shape)}, weight {tuple(w.shape)}, bias {None if bias is None else tuple(bias.shape)}')
+        w = w.contiguous()
+        if bias is not None:
+            _require_gpu(bias, 'linear bias')
+            bias = bias.contiguous()
+        M, K = x.shape
+        N = w.shape[0]
+        y = torch.empty((M, N), device=x.device, dtype=torch.float32)
+        check(L.y4_linear_fwd_f32(_ptr(x), ldx, _ptr(w), _ptr(bias), _ptr(y), N, M, K, N, _stream()), 'linear_fwd')
+        ctx.save_for_backward(x, w)
+        ctx.ldx = ldx
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        L = lib()
+        x, w = ctx.saved_tensors
+        M, K = x.shape
+        N = w.shape[0]
+        g, ldg = _rows(g, 'linear grad')
+        need = ctx.needs_input_grad
+        dx = torch.empty((M, K), device=g.device, dtype=torch.float32) if need[0] else None
+        dw = torch.empty((N, K), device=g.device, dtype=torch.float32) if need[1] else None
+        db = torch.empty((N,), device=g.device, dtype=torch.float32) if (ctx.has_bias and need[2]) else None
+        if dx is not None or dw is not None or db is not None:
+            check(L.y4_linear_bwd_f32(_ptr(x), ctx.ldx, _ptr(w), _ptr(g), ldg, _ptr(dx), K, _ptr(dw), _ptr(db), M, K, N,
+                                      _stream()), 'linear_bwd')
+        return dx, dw, db
+
+
+class CESmoothFn(torch.autograd.Function):
+    """nn.CrossEntropyLoss(label_smoothing=eps) (mean, ignore_index -100), darknet/main_amp.py:184."""
+
+    @staticmethod
+    def forward(ctx, logits, target, smoothing):
+        L = lib()
+        logits, ldl = _rows(logits, 'cross-entropy logits')
+        B, N = logits.shape
+        target = _labels(target, B, logits.device, 'cross-entropy')
+        row = torch.empty((B,), device=logits.device, dtype=torch.float32)
+        out = torch.empty((2,), device=logits.device, dtype=torch.float64)
+        check(L.y4_ce_smooth_fwd_f32(_ptr(logits), ldl, _ptr(target), B, N, float(smoothing), _ptr(row), _ptr(out), _stream()),
+              'ce_smooth_fwd')
+        ctx.save_for_backward(logits, target, out)
+        ctx.meta = (ldl, float(smoothing))
+        return out[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, gloss):
+        L = lib()
+        logits, target, out = ctx.saved_tensors
+        ldl, smoothing = ctx.meta
+        B, N = logits.shape
+        gs = gloss.detach().to(torch.float32).reshape(1).contiguous()
+        d = torch.empty((B, N), device=logits.device, dtype=torch.float32)
+        check(L.y4_ce_smooth_bwd_f32(_ptr(logits), ldl, _ptr(target), _ptr(out), _ptr(gs), _ptr(d), N, B, N, smoothing,
+                                     _stream()), 'ce_smooth_bwd')
+        return d, None, None
+
+
+def topk_correct(logits, target, ks, want_rank=False):
+    """int32 device tensor: for each k in ks the number of rows whose label is among the k largest logits (ties go to the
+    lower index); with want_rank also the int32 [B] ranks.  No host sync."""
+    L = lib()
+    logits, ldl = _rows(logits.detach(), 'top-k logits')
+    B, N = logits.shape
+    target = _labels(target, B, logits.device, 'top-k')
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= 8:
+        raise Y4Error(f'top-k: between 1 and 8 values of k, got {len(ks)}')
+    correct = torch.empty((len(ks),), device=logits.device, dtype=torch.int32)
+    rank = torch.empty((B,), device=logits.device, dtype=torch.int32) if want_rank else None
+    check(L.y4_topk_correct_f32(_ptr(logits), ldl, _ptr(target), B, N, int_array(ks), len(ks), _ptr(correct), _ptr(rank),
+                                _stream()), 'topk_correct')
+    return (correct, rank) if want_rank else correct
