@@ -458,6 +458,33 @@ int y4_adam_multi_step_f32(const void* chunks_dev, int nchunks, const float* hyp
                            float beta1, float beta2, float eps, float grad_scale, void* stream);
 int y4_sgd_multi_step_f32(const void* chunks_dev, int nchunks, const float* hyper_host, int nhyper,
                           float grad_scale, void* stream);
+/* Guarded steps: global grad-norm clipping (torch.nn.utils.clip_grad_norm_) and the skip of a step whose gradients
+ * are not finite, decided on the device (no host sync; fixed-order sums, no float atomics: bit-identical run to run).
+ * Guard record: 4 doubles in device memory {total_norm, coef, applied (1.0 / 0.0), skipped_total}; the caller zeroes
+ * it once, skipped_total counts on.  Sequence per step, over the SAME chunk table as the step:
+ *   y4_grad_sumsq_multi_f32: partials[c] = sum_i ((double)fl32(g_i * grad_scale))^2 for every chunk c (the value
+ *     squared is the fp32 value the step kernels use; 16-byte loads when the chunk's g is 16-byte aligned, scalar
+ *     otherwise; inf / NaN travel through the sums);
+ *   y4_grad_guard_f32: total_norm = sqrt(sum of partials[0..nchunks)), applied = isfinite(total_norm),
+ *     coef = (max_norm > 0 and finite) ? min(1, max_norm / (total_norm + 1e-6)) : 1, in double; coef = 1 when not
+ *     applied; skipped_total += !applied;
+ *   y4_{adam,sgd}_multi_step_guarded_f32: the multi-tensor step with grad_scale * (float)coef; writes nothing when
+ *     applied == 0; with coef == 1 bit-identical to the unguarded entry points.  guard is required.
+ * Errors before any launch: Y4_ERR_NULL for a NULL pointer, Y4_ERR_SHAPE for nchunks <= 0 or a table / partials /
+ * guard pointer that is not 8-byte aligned. */
+int y4_grad_sumsq_multi_f32(const void* chunks_dev, int nchunks, float grad_scale, double* partials /* [nchunks] */,
+                            void* stream);
+int y4_grad_guard_f32(const double* partials, int nchunks, double max_norm, double* guard, void* stream);
+int y4_adam_multi_step_guarded_f32(const void* chunks_dev, int nchunks, const float* hyper_host, int nhyper,
+                                   float beta1, float beta2, float eps, float grad_scale, const double* guard,
+                                   void* stream);
+int y4_sgd_multi_step_guarded_f32(const void* chunks_dev, int nchunks, const float* hyper_host, int nhyper,
+                                  float grad_scale, const double* guard, void* stream);
+/* Exponential moving average of a list of tensors in one launch: e = e + one_minus_decay * (s - e) over the same
+ * 48-byte records with p = EMA tensor e, g = live tensor s (m, v, hyper_row unused: 0).  With a guard record whose
+ * applied == 0 nothing is written (the step it followed was skipped).  one_minus_decay outside [0, 1]: Y4_ERR_SHAPE. */
+int y4_ema_multi_f32(const void* chunks_dev, int nchunks, float one_minus_decay, const double* guard /* nullable */,
+                     void* stream);
 
 /* ---------------------------------------------------------------- eval input pipeline ("next" row 4)
  * One image: src is uint8 HWC (3 channels, row pitch in bytes), as cv2.imread hands it to the reference.

@@ -99,6 +99,11 @@ PROTOTYPES = {
     'y4_adam_hyper_f32': (I, [F, F, F, F, I, P]),
     'y4_adam_multi_step_f32': (I, [P, I, P, I, F, F, F, F, P]),
     'y4_sgd_multi_step_f32': (I, [P, I, P, I, F, P]),
+    'y4_grad_sumsq_multi_f32': (I, [P, I, F, P, P]),
+    'y4_grad_guard_f32': (I, [P, I, c_double, P, P]),
+    'y4_adam_multi_step_guarded_f32': (I, [P, I, P, I, F, F, F, F, P, P]),
+    'y4_sgd_multi_step_guarded_f32': (I, [P, I, P, I, F, P, P]),
+    'y4_ema_multi_f32': (I, [P, I, F, P, P]),
     'y4_preprocess_u8_f32': (I, [P, I, I, L, I, P, L, L, L, I, P]),
     'y4_avgpool_global_fwd_f32': (I, [P, I, P, I, I, I, I, P]),
     'y4_avgpool_global_bwd_f32': (I, [P, I, P, I, I, I, I, P]),

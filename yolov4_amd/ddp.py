@@ -22,6 +22,10 @@ heals the gradient slots (an `optimizer.zero_grad()` with torch's default set_to
 `p.grad` from the flat buffers), the first gradient hook of a backward queues an end-of-backward
 callback that waits for the exchanges.  `zero_grad()`, `rearm()` and `finish_backward()` remain
 callable (idempotent) for explicit control, e.g. gradient accumulation without exchange.
+
+Guarded optimizer steps (FusedAdam / FusedSGD with max_grad_norm / skip_nonfinite) need nothing from this class:
+`optimizer.step()` runs after `finish_backward()`, when every rank holds the same reduced gradients in its buckets, so
+every rank computes the same norm, the same clip coefficient and the same skip decision: no extra collective.
 """
 import torch
 import torch.distributed as dist

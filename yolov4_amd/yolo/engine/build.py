@@ -45,11 +45,13 @@ def reduce_tensor(args, tensor):
     return rt
 
 
-def train_step(cfg, model, criterion, optimizer, input, target, device=None, step_index=0, len_epoch=None, epoch=0):
+def train_step(cfg, model, criterion, optimizer, input, target, device=None, step_index=0, len_epoch=None, epoch=0,
+               ema=None):
     """One micro-batch of build.py:55-69.  Returns the (already divided) loss tensor.
 
     step_index: i of the reference loop; the optimizer steps when (i + 1) % ACCUMULATION_STEPS == 0 or at the last
-    batch of the epoch (len_epoch)."""
+    batch of the epoch (len_epoch).  ema: optional ModelEMA (yolo/util/ema.py), updated after every optimizer step; it
+    reads the optimizer's guard record on the device, so a skipped step leaves the average alone."""
     accumulation_steps = int(cfg['TRAIN']['ACCUMULATION_STEPS'])
     if cfg['LR_SCHEDULER']['IS_WARMUP'] and epoch < int(cfg['LR_SCHEDULER']['WARMUP_EPOCH']) and len_epoch:
         adjust_learning_rate(cfg, optimizer, epoch, step_index, len_epoch)                       # :56-57
@@ -68,11 +70,14 @@ def train_step(cfg, model, criterion, optimizer, input, target, device=None, ste
         with trace.range('y4.optimizer'):
             optimizer.step()                                                                     # :67-69
             optimizer.zero_grad()
+            if ema is not None:
+                ema.update(model.module if hasattr(model, 'accumulating') else model, getattr(optimizer, 'guard', None))
     return loss
 
 
-def train(args, cfg, train_loader, model, criterion, optimizer, device=None, epoch=0, log=None):
-    """build.py:41-107.  `log`: optional callable(str) (the reference logs through its rank-0 logger)."""
+def train(args, cfg, train_loader, model, criterion, optimizer, device=None, epoch=0, log=None, ema=None):
+    """build.py:41-107.  `log`: optional callable(str) (the reference logs through its rank-0 logger); `ema`: optional
+    ModelEMA handed to every train_step."""
     batch_time, losses = AverageMeter(), AverageMeter()
     model.train()
     end = time.time()
@@ -81,7 +86,7 @@ def train(args, cfg, train_loader, model, criterion, optimizer, device=None, epo
     print_freq = int(getattr(args, 'print_freq', 10))
     world = int(getattr(args, 'world_size', 1))
     for i, (input, target) in enumerate(train_loader):
-        loss = train_step(cfg, model, criterion, optimizer, input, target, device, i, n, epoch)
+        loss = train_step(cfg, model, criterion, optimizer, input, target, device, i, n, epoch, ema)
         if (i + 1) % print_freq == 0:
             reduced = reduce_tensor(args, loss.data) if getattr(args, 'distributed', False) else loss.data
             losses.update(float(reduced), input.size(0))                   # host <-> device sync, as the reference

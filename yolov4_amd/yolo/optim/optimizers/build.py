@@ -34,21 +34,76 @@ def filter_weight(cfg: Dict, module: Module):
 CHUNK = 1 << 16          # elements per table record of the multi-tensor kernels
 
 
+def same_layout(t, p):
+    return t.stride() == p.stride() and t.dtype == p.dtype and t.device == p.device
+
+
+def dense_like(t, p):
+    """t re-laid in p's dense memory order (the multi-tensor kernels pair elements by raw offset)."""
+    if same_layout(t, p):
+        return t
+    return torch.empty_like(p, memory_format=torch.preserve_format).copy_(t)
+
+
 class _MultiTensorOptimizer(torch.optim.Optimizer):
     """Shared plumbing of the fused optimizers: every parameter, its gradient and its state tensors are cut into
     runs of CHUNK elements listed in ONE device table ({p, g, m, v, n, hyper row} records, include/yolov4_amd.h);
     a step is one kernel launch over that table.  The table is rebuilt only when a pointer changes (gradients that
     live in BucketedDDP's flat buckets never move, so in steady state nothing is uploaded but 16 floats of
-    per-group scalars)."""
+    per-group scalars).
+
+    Guarded steps (max_grad_norm and / or skip_nonfinite set; both off: exactly the one launch above, no guard memory).
+    step() then issues three launches over the same table, none of which synchronises with the host:
+    y4_grad_sumsq_multi_f32 (one double per chunk), y4_grad_guard_f32 (the 4-double record {total_norm, coef,
+    applied, skipped_total} in `self.guard`) and the guarded step, which multiplies the gradients by `coef`
+    (torch.nn.utils.clip_grad_norm_'s coefficient; always 1 with max_grad_norm=None) and writes nothing when the norm
+    is inf / NaN.  Every sum runs in a fixed order: the record is bit-identical run to run.
+
+    Step-number policy: a skipped step still consumes a step number.  The host cannot know about the skip without a
+    sync, so state['step'], Adam's bias-correction row, SGD's first-step flag and the LR schedule advance as usual.
+    (SGD whose first step is skipped stays correct: the next step computes momentum * 0 + g == g.)
+    `guard_state()` is the only call that synchronises; it is meant for a log line that already does."""
 
     n_state = 2
 
-    def __init__(self, params, defaults):
+    def __init__(self, params, defaults, max_grad_norm=None, skip_nonfinite=False):
         super().__init__(params, defaults)
         self.grad_scale = 1.0
         self._table = None
         self._table_key = None
         self.launches = 0            # kernel launches issued by step() so far (tests / profiling)
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f'max_grad_norm must be positive or None, got {max_grad_norm}')
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.guard = None            # device tensor of 4 doubles, allocated by the first guarded step
+        self._partials = None
+
+    @property
+    def guarded(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def guard_state(self):
+        """{'total_norm', 'coef', 'applied', 'skipped'} of the last guarded step as Python numbers (synchronises)."""
+        if self.guard is None:
+            raise ops.Y4Error(f'{type(self).__name__}: no guarded step has run (max_grad_norm / skip_nonfinite are off)')
+        total, coef, applied, skipped = self.guard.tolist()
+        return {'total_norm': total, 'coef': coef, 'applied': bool(applied), 'skipped': int(skipped)}
+
+    def _guard_launches(self, table, nchunks, dev):
+        """sumsq + guard over the step's table; returns the record's pointer for the guarded step."""
+        if self.guard is None or self.guard.device != dev:
+            self.guard = torch.zeros(4, dtype=torch.float64, device=dev)
+        if self._partials is None or self._partials.numel() != nchunks or self._partials.device != dev:
+            self._partials = torch.empty(nchunks, dtype=torch.float64, device=dev)
+        # an infinite max_norm never clips, as in clip_grad_norm_; without max_grad_norm only the skip acts (coef == 1)
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else 0.0
+        check(lib().y4_grad_sumsq_multi_f32(ops._ptr(table), nchunks, float(self.grad_scale), ops._ptr(self._partials),
+                                            ops._stream()), 'grad_sumsq_multi')
+        check(lib().y4_grad_guard_f32(ops._ptr(self._partials), nchunks, max_norm, ops._ptr(self.guard), ops._stream()),
+              'grad_guard')
+        self.launches += 2
+        return ops._ptr(self.guard)
 
     def zero_grad(self, set_to_none: bool = False):
         """Default differs from torch (set_to_none=True): gradients that live in BucketedDDP's flat buckets are
@@ -73,16 +128,12 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
                 p.grad.requires_grad_(False)
                 p.grad.zero_()
 
-    @staticmethod
-    def _same_layout(t, p):
-        return t.stride() == p.stride() and t.dtype == p.dtype and t.device == p.device
+    _same_layout = staticmethod(same_layout)
 
     def _dense_like(self, t, p):
-        """t re-laid in p's dense memory order (the kernels pair elements by raw offset): e.g. Adam moments
-        restored by load_state_dict from a reference checkpoint are contiguous OIHW while the parameter is KRSC."""
-        if self._same_layout(t, p):
-            return t
-        return torch.empty_like(p, memory_format=torch.preserve_format).copy_(t)
+        """dense_like: e.g. Adam moments restored by load_state_dict from a reference checkpoint are contiguous OIHW
+        while the parameter is KRSC."""
+        return dense_like(t, p)
 
     def _state_tensors(self, p, group):
         raise NotImplementedError
@@ -90,7 +141,7 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
     def _hyper_row(self, group, step):
         raise NotImplementedError
 
-    def _launch(self, table, nchunks, hyper, nh, group0):
+    def _launch(self, table, nchunks, hyper, nh, guard=None):
         raise NotImplementedError
 
     @torch.no_grad()
@@ -133,7 +184,8 @@ class _MultiTensorOptimizer(torch.optim.Optimizer):
             self._table = host.to(dev)
             self._table_key = key
         flat = [v for row in hyper for v in row]
-        self._launch(self._table, len(rows), ops.float_array(flat), len(hyper))
+        guard = self._guard_launches(self._table, len(rows), dev) if self.guarded else None
+        self._launch(self._table, len(rows), ops.float_array(flat), len(hyper), guard)
         self.launches += 1
         del keep
         return loss
@@ -144,8 +196,10 @@ class FusedAdam(_MultiTensorOptimizer):
 
     _hyper_keys = ('lr', 'weight_decay')
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None,
+                 skip_nonfinite=False):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm,
+                         skip_nonfinite)
 
     def _state_tensors(self, p, group):
         st = self.state[p]
@@ -167,11 +221,16 @@ class FusedAdam(_MultiTensorOptimizer):
               'adam_hyper')
         return list(out)
 
-    def _launch(self, table, nchunks, hyper, nh):
+    def _launch(self, table, nchunks, hyper, nh, guard=None):
         g0 = self.param_groups[0]
         if any(g['betas'] != g0['betas'] or g['eps'] != g0['eps'] for g in self.param_groups):
             raise ops.Y4Error('FusedAdam: betas / eps must be the same in every param group')
         b1, b2 = g0['betas']
+        if guard is not None:
+            check(lib().y4_adam_multi_step_guarded_f32(ops._ptr(table), nchunks, hyper, nh, float(b1), float(b2),
+                                                       float(g0['eps']), float(self.grad_scale), guard, ops._stream()),
+                  'adam_multi_step_guarded')
+            return
         check(lib().y4_adam_multi_step_f32(ops._ptr(table), nchunks, hyper, nh, float(b1), float(b2), float(g0['eps']),
                                            float(self.grad_scale), ops._stream()), 'adam_multi_step')
 
@@ -181,8 +240,8 @@ class FusedSGD(_MultiTensorOptimizer):
 
     _hyper_keys = ('lr', 'momentum', 'weight_decay')
 
-    def __init__(self, params, lr=0.1, momentum=0.9, weight_decay=1e-5):
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+    def __init__(self, params, lr=0.1, momentum=0.9, weight_decay=1e-5, max_grad_norm=None, skip_nonfinite=False):
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay), max_grad_norm, skip_nonfinite)
 
     def _state_tensors(self, p, group):
         st = self.state[p]
@@ -196,7 +255,11 @@ class FusedSGD(_MultiTensorOptimizer):
     def _hyper_row(self, group, step):
         return [float(group['lr']), float(group['momentum']), float(group['weight_decay']), 1.0 if step == 1 else 0.0]
 
-    def _launch(self, table, nchunks, hyper, nh):
+    def _launch(self, table, nchunks, hyper, nh, guard=None):
+        if guard is not None:
+            check(lib().y4_sgd_multi_step_guarded_f32(ops._ptr(table), nchunks, hyper, nh, float(self.grad_scale), guard,
+                                                      ops._stream()), 'sgd_multi_step_guarded')
+            return
         check(lib().y4_sgd_multi_step_f32(ops._ptr(table), nchunks, hyper, nh, float(self.grad_scale), ops._stream()),
               'sgd_multi_step')
 
@@ -205,11 +268,16 @@ def build_optimizer(cfg: Dict, model: Module):
     optimizer_type = cfg['OPTIMIZER']['TYPE']
     lr = float(cfg['OPTIMIZER']['LR'])
     groups = filter_weight(cfg, model)
+    # not in the reference: CLIP_GRAD_NORM (global L2 norm bound) / SKIP_NONFINITE (drop a step with inf / NaN gradients);
+    # absent keys leave the plain one-launch step
+    clip = cfg['OPTIMIZER'].get('CLIP_GRAD_NORM')
+    guard = dict(max_grad_norm=None if clip is None else float(clip),
+                 skip_nonfinite=bool(cfg['OPTIMIZER'].get('SKIP_NONFINITE', False)))
     if 'SGD' == optimizer_type:                                                # build.py:25-28, sgd.py:14-15
         optimizer = FusedSGD(groups, lr=lr, momentum=float(cfg['OPTIMIZER']['MOMENTUM']),
-                             weight_decay=float(cfg['OPTIMIZER']['DECAY']))
+                             weight_decay=float(cfg['OPTIMIZER']['DECAY']), **guard)
     elif 'ADAM' == optimizer_type:
-        optimizer = FusedAdam(groups, lr=lr, betas=(0.9, 0.999), eps=1e-08)      # adam.py:14-15
+        optimizer = FusedAdam(groups, lr=lr, betas=(0.9, 0.999), eps=1e-08, **guard)      # adam.py:14-15
     else:
         raise ValueError(f"{optimizer_type} does not support.")
     optimizer.zero_grad()            # build.py:34; in place: gradient slots of a BucketedDDP wrapper stay attached
