@@ -427,7 +427,8 @@ int y4_nms_f32(const float* boxes, const float* scores /* may be NULL */, long l
 int y4_bboxes_iou_f32(const float* boxes_a, long long Na, const float* boxes_b, long long Nb, int xyxy, float* iou,
                       void* stream);
 /* Mish.forward (darknet/darknet.py:14-20) and the other activations of ConvBNAct as a flat elementwise sweep over a
- * dense tensor of n floats (act = Y4_ACT_*); backward: dx = dy * act'(x). */
+ * dense tensor of n floats (act = Y4_ACT_*); backward: dx = dy * act'(x).  Mish here keeps the denormal values of e^x
+ * (x < -87.3), which the fused forms flush to zero; mish'(x) is exactly 1 for x > 20 (+inf included), NaN for NaN. */
 int y4_act_fwd_f32(const float* x, float* y, long long n, int act, void* stream);
 int y4_act_bwd_f32(const float* x, const float* dy, float* dx, long long n, int act, void* stream);
 /* Upsample.forward (yolo/model/yolov4.py:82-90) for any target size, NHWC with pitches.  integer_factor = 0: the

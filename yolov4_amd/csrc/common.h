@@ -36,8 +36,21 @@ struct Y4DynLds {
 // torch (returns x above it) coincides with the ratio being exactly 1.0f there.
 // One v_exp_f32 + one v_rcp_f32 (both ~1 ulp): these kernels are HBM-bound only if the
 // activation costs a handful of VALU ops per element.
-__device__ __forceinline__ float y4_mish(float x) {
-    const float n = __expf(fminf(x, 20.0f));
+//
+// n = e^min(x, 20).  v_exp_f32 flushes a denormal RESULT to zero, so below x = -87.34 (e^x < 2^-126) n is 0 and Mish and its
+// derivative come out as -0 / 0 where they are x e^x and (1 + x) e^x: up to 1.2e-36 in magnitude, 100 times the smallest
+// normal number.  DENORM = true raises the exponent by 64 below 2^-126 and scales the result back (both exact: powers of two;
+// the same bits as DENORM = false everywhere else) for five more VALU operations.  The flat activation kernels take it; the
+// fused epilogues and the BatchNorm sweeps, which have no VALU operation to spare, keep the flush and with it an ABSOLUTE
+// error of at most 1.2e-36 for pre-activations in [-103.3, -87.34].
+template <bool DENORM = false> __device__ __forceinline__ float y4_mish_exp(float x) {
+    if constexpr (!DENORM) return __expf(fminf(x, 20.0f));
+    const float t = fminf(x, 20.0f) * 1.44269504088896341f;              // as __expf: 2^(x log2 e)
+    const bool low = t < -126.0f;
+    return __builtin_amdgcn_exp2f(low ? t + 64.0f : t) * (low ? 0x1p-64f : 1.0f);
+}
+template <bool DENORM = false> __device__ __forceinline__ float y4_mish(float x) {
+    const float n = y4_mish_exp<DENORM>(x);
     const float w = n * (n + 2.0f);
     return x * (w * __frcp_rn(w + 2.0f));
 }
@@ -45,25 +58,29 @@ __device__ __forceinline__ float y4_mish(float x) {
 // t = w / d, 1 - t^2 = 4 (w + 1) / d^2 = 4 (n + 1)^2 / d^2, sigmoid = n / (n + 1)  =>  (1 - t^2) sigmoid = 4 n (n + 1) / d^2,
 // so the derivative is (w + 4 x n (n + 1) / d) / d: ONE v_rcp_f32 beside the v_exp_f32 (no cancellation: every term but x
 // is positive).  The BatchNorm backward sweeps evaluate this twice per element and run close to the VALU rate with it.
-__device__ __forceinline__ float y4_mish_grad(float x) {
-    const float n = __expf(fminf(x, 20.0f));
+// Above the clamp n stays e^20 while x grows: the second term would read 4 x / n^2 instead of 4 x e^-2x -- 1.7 at
+// x = 1e17, +inf from 1.45e21 on (and then NaN for a zero upstream gradient) -- where the derivative is 1 to 4e-16.  Hence
+// the select; a NaN compares false and takes the formula's NaN.
+template <bool DENORM = false> __device__ __forceinline__ float y4_mish_grad(float x) {
+    const float n = y4_mish_exp<DENORM>(x);
     const float w = n * (n + 2.0f);
     const float rd = __frcp_rn(w + 2.0f);
     const float q = fmaf(n, n, n);                         // n (n + 1)
-    return fmaf(4.0f * (x * q), rd, w) * rd;
+    const float d = fmaf(4.0f * (x * q), rd, w) * rd;
+    return x > 20.0f ? 1.0f : d;
 }
-__device__ __forceinline__ float y4_act(float x, int act) {
+template <bool DENORM = false> __device__ __forceinline__ float y4_act(float x, int act) {
     switch (act) {
         case Y4_ACT_LEAKY: return x > 0.0f ? x : 0.1f * x;
-        case Y4_ACT_MISH: return y4_mish(x);
+        case Y4_ACT_MISH: return y4_mish<DENORM>(x);
         case Y4_ACT_RELU: return x < 0.0f ? 0.0f : x;      // (not fmaxf: a NaN stays a NaN, as in torch)
         default: return x;
     }
 }
-__device__ __forceinline__ float y4_act_grad(float x, int act) {
+template <bool DENORM = false> __device__ __forceinline__ float y4_act_grad(float x, int act) {
     switch (act) {
         case Y4_ACT_LEAKY: return x > 0.0f ? 1.0f : 0.1f;
-        case Y4_ACT_MISH: return y4_mish_grad(x);
+        case Y4_ACT_MISH: return y4_mish_grad<DENORM>(x);
         case Y4_ACT_RELU: return x > 0.0f ? 1.0f : 0.0f;
         default: return 1.0f;
     }

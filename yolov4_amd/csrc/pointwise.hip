@@ -884,7 +884,8 @@ __global__ __launch_bounds__(PW_THREADS) void upsample_nearest_bwd_kernel(const 
 }
 
 // ---------------------------------------------------------------- standalone activation (Mish.forward, darknet.py:14-20)
-// Flat elementwise sweep over a dense tensor of n floats; the same device functions as the fused epilogues.
+// Flat elementwise sweep over a dense tensor of n floats; the same device functions as the fused epilogues, with the
+// exponential's denormal results kept (common.h, y4_mish_exp): these kernels have VALU time to spare.
 __global__ __launch_bounds__(PW_THREADS) void act_fwd_flat_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                   long long n, int act) {
     const long long n4 = n >> 2;
@@ -895,12 +896,12 @@ __global__ __launch_bounds__(PW_THREADS) void act_fwd_flat_kernel(const float* _
         for (long long i = t; i < n4; i += stride) {
             f32x4 v = ld4(x + 4 * i);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = y4_act(v[e], act);
+            for (int e = 0; e < 4; ++e) v[e] = y4_act<true>(v[e], act);
             st4(y + 4 * i, v);
         }
         done = n4 << 2;
     }
-    for (long long i = done + t; i < n; i += stride) y[i] = y4_act(x[i], act);
+    for (long long i = done + t; i < n; i += stride) y[i] = y4_act<true>(x[i], act);
 }
 __global__ __launch_bounds__(PW_THREADS) void act_bwd_flat_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                   float* __restrict__ dx, long long n, int act) {
@@ -913,12 +914,12 @@ __global__ __launch_bounds__(PW_THREADS) void act_bwd_flat_kernel(const float* _
             const f32x4 v = ld4(x + 4 * i), g = ld4(dy + 4 * i);
             f32x4 o;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = g[e] * y4_act_grad(v[e], act);
+            for (int e = 0; e < 4; ++e) o[e] = g[e] * y4_act_grad<true>(v[e], act);
             st4(dx + 4 * i, o);
         }
         done = n4 << 2;
     }
-    for (long long i = done + t; i < n; i += stride) dx[i] = dy[i] * y4_act_grad(x[i], act);
+    for (long long i = done + t; i < n; i += stride) dx[i] = dy[i] * y4_act_grad<true>(x[i], act);
 }
 
 inline int grid_for(long long total, int cap = 256 * 16) {
