@@ -495,6 +495,61 @@ int y4_ema_multi_f32(const void* chunks_dev, int nchunks, float one_minus_decay,
 int y4_preprocess_u8_f32(const void* src, int src_h, int src_w, long long src_pitch_bytes, int swap_rb,
                          float* dst, long long dst_sc, long long dst_sh, long long dst_sw, int S, void* stream);
 
+/* ---------------------------------------------------------------- training input pipeline
+ * The reference's per-sample CPU augmentation (yolo/data/transform.py:385-427 _get_train_item: crop-and-pad with a mean
+ * fill, flip, resize to SxS, HSV "colour dithering", 4-image mosaic) as two launches per BATCH.  The random draws are made
+ * on the host; both entry points are deterministic functions of a descriptor table.
+ *
+ * One record per source image (uint8 HWC, 3 channels, row pitch in bytes; 1 <= h, w <= 65535): */
+typedef struct y4_aug_src {
+    const void* src;                /* device pointer */
+    int h, w;
+    long long pitch;                /* bytes, >= 3 * w */
+    int swap_rb;                    /* 1: the source is BGR, the output RGB (transform.py:402) */
+    int crop_left, crop_top;        /* origin of the crop rectangle in the source; negative = pad (mean fill) */
+    int crop_w, crop_h;             /* >= 1; w - crop_left - crop_right, h - crop_top - crop_bottom */
+    int flip;                       /* mirror the crop image in x */
+    int color;                      /* apply the HSV step (when dhue, dsat, dexp are not the identity) */
+    float dhue, dsat, dexp;         /* h += 179 * dhue, s *= dsat, v *= dexp; |dhue| <= 4, all finite */
+    int win_x, win_y;               /* origin, in the resized SxS image, of the window the tile shows */
+} y4_aug_src;
+/* One record per output sample: n_src = 1 (the single source covers the output, cuts unused but still checked) or 4 (tiles
+ * 0..3 = top-left, top-right, bottom-left, bottom-right of the cut point); its sources are table[first .. first + n_src). */
+typedef struct y4_aug_sample {
+    int cut_x, cut_y, n_src, first;
+} y4_aug_sample;
+/* Both tables are passed twice: *_dev is what the kernels read, *_host the same bytes in host memory, which the entry point
+ * checks before it launches anything (the caller copies host -> device on the same stream; no synchronisation is needed).
+ *
+ * y4_augment_means_u8: sums_dev[i][k] = exact integer sum of channel k (memory order) of source i, by integer adds and
+ *   integer atomics only (independent of the grid); < 2^40 for any accepted image.  sums_dev is zeroed by the call.
+ * y4_augment_mosaic_u8_f32: dst[b*dst_sb + c*dst_sc + oy*dst_sh + ox*dst_sw] (strides in elements), per output pixel:
+ *   1. tile q = (oy >= cut_y) * 2 + (ox >= cut_x) (0 when n_src == 1); position in that tile's resized image
+ *      (ry, rx) = (oy - tile_y0 + win_y, ox - tile_x0 + win_x);
+ *   2. bilinear taps in the crop image as OpenCV's floating linear resize takes them: f = (float)((r + 0.5) * scale - 0.5),
+ *      scale = 1.0 / ((double)S / (double)crop_n); s = floor(f), fraction f - s in fp32; in x the fraction is zeroed and s
+ *      clamped where s < 0 or s >= crop_w - 1; in y both rows are clamped and the fraction kept; fp32 weights 1 - f and f,
+ *      horizontal pass first.  No fixed-point path, no rounding to 8 bits (the reference resizes a float64 image);
+ *   3. each tap: cx = crop_w - 1 - sx when flip; source position (cy + crop_top, cx + crop_left); inside the source the
+ *      uint8 channel (after the B/R swap), outside the channel's mean sum / (h * w), formed in double, not rounded to 8 bits;
+ *   4. when color && (dsat != 1 || dexp != 1 || dhue != 0), on the 0..255 scale (OpenCV's float RGB2HSV / HSV2RGB):
+ *      v = max, d = v - min, s = d / (|v| + FLT_EPSILON), k = 60 / (d + FLT_EPSILON); h = (g-b)k if v == r, else
+ *      (b-r)k + 120 if v == g, else (r-g)k + 240; h += 360 if h < 0; then h += 179*dhue, s *= dsat (not clamped),
+ *      v *= dexp; back: s == 0 -> r = g = b = v, else h /= 60 wrapped into [0, 6) by repeated +-6, i = floor(h), f = h - i,
+ *      candidates v, v(1-s), v(1-sf), v(1-s(1-f)) in the usual sector order; result clipped to [0, 255].  Without the HSV
+ *      step there is no clip;
+ *   5. value / 255 in fp32.
+ * Errors before any launch: Y4_ERR_NULL for a NULL pointer (a record's src included); Y4_ERR_SHAPE for B < 1, S < 1,
+ * S or B > 65535, n_src not 1 or 4, first outside the table, h or w outside [1, 65535], pitch < 3w, crop_w or crop_h < 1,
+ * crop offsets or sizes beyond 2^24, cuts outside [0, S], a window that does not fit (win + tile extent > S, win < 0),
+ * |dhue| > 4 or a non-finite colour parameter. */
+int y4_augment_means_u8(const y4_aug_src* table_dev, const y4_aug_src* table_host, int n_src,
+                        unsigned long long* sums_dev /* [n_src][3] */, void* stream);
+int y4_augment_mosaic_u8_f32(const y4_aug_src* table_dev, const y4_aug_src* table_host, int n_table,
+                             const y4_aug_sample* samples_dev, const y4_aug_sample* samples_host, int B,
+                             const unsigned long long* sums_dev, float* dst, long long dst_sb, long long dst_sc,
+                             long long dst_sh, long long dst_sw, int S, void* stream);
+
 /* ---------------------------------------------------------------- ImageNet classifier (backbone pre-training)
  * The four operations behind the backbone in CSPDarknet53 (darknet/darknet.py:164-193) and its training script
  * (darknet/main_amp.py:184 CrossEntropyLoss(label_smoothing=0.1), :549-562 accuracy).  fp32 throughout; outputs are

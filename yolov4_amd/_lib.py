@@ -105,6 +105,8 @@ PROTOTYPES = {
     'y4_sgd_multi_step_guarded_f32': (I, [P, I, P, I, F, P, P]),
     'y4_ema_multi_f32': (I, [P, I, F, P, P]),
     'y4_preprocess_u8_f32': (I, [P, I, I, L, I, P, L, L, L, I, P]),
+    'y4_augment_means_u8': (I, [P, P, I, P, P]),
+    'y4_augment_mosaic_u8_f32': (I, [P, P, I, P, P, I, P, P, L, L, L, L, I, P]),
     'y4_avgpool_global_fwd_f32': (I, [P, I, P, I, I, I, I, P]),
     'y4_avgpool_global_bwd_f32': (I, [P, I, P, I, I, I, I, P]),
     'y4_linear_fwd_f32': (I, [P, I, P, P, P, I, I, I, I, P]),
@@ -113,6 +115,21 @@ PROTOTYPES = {
     'y4_ce_smooth_bwd_f32': (I, [P, I, P, P, P, P, I, I, I, c_double, P]),
     'y4_topk_correct_f32': (I, [P, I, P, I, I, P, I, P, P, P]),
 }
+
+
+
+class AugSrc(ctypes.Structure):
+    """y4_aug_src (72 bytes)"""
+    _fields_ = [('src', c_void_p), ('h', c_int), ('w', c_int), ('pitch', c_longlong), ('swap_rb', c_int),
+                ('crop_left', c_int), ('crop_top', c_int), ('crop_w', c_int), ('crop_h', c_int), ('flip', c_int),
+                ('color', c_int), ('dhue', c_float), ('dsat', c_float), ('dexp', c_float), ('win_x', c_int),
+                ('win_y', c_int)]
+
+
+class AugSample(ctypes.Structure):
+    """y4_aug_sample (16 bytes)"""
+    _fields_ = [('cut_x', c_int), ('cut_y', c_int), ('n_src', c_int), ('first', c_int)]
+
 
 _lib = None
 
