@@ -587,6 +587,53 @@ int y4_ce_smooth_bwd_f32(const float* logits, int ldl, const long long* target, 
 int y4_topk_correct_f32(const float* logits, int ldl, const long long* target, int B, int N, const int* ks_host, int nk,
                         int* correct /* [nk] */, int* rank /* [B] or NULL */, void* stream);
 
+/* ---------------------------------------------------------------- COCO bbox evaluation
+ * The COCOeval protocol the reference runs on the records of validate() (yolo/engine/build.py:172-188: evaluate,
+ * accumulate; the summary is twelve means the caller takes on the host), as two launches.  T = 10 IoU thresholds, R = 101
+ * recall thresholds, A = 4 area ranges, M = 3 maxDets; the threshold tables are the CALLER's fp64 arrays (device memory),
+ * never recomputed here.  A cell is an (image, category) pair with at least one gt or one detection; cells are numbered
+ * category-major, then by image.  Both calls read CSR offsets twice: *_dev is what the kernels read, *_host the same ints
+ * in host memory, checked before anything is launched.
+ *
+ * y4_coco_match_f64: per cell, its detections (dbox rows [x, y, w, h], det_off[cell] .. det_off[cell + 1], already sorted by
+ *   score descending and cut to the first 100: a row's position in its cell is its rank) against its gts (gbox rows, garea =
+ *   the annotation's area field, gcrowd = iscrowd, in annotation order).  IoU in fp64 in this order, no fused multiply-add:
+ *     w = min(dx+dw, gx+gw) - max(dx, gx); h likewise; w <= 0 or h <= 0 -> 0; i = w*h;
+ *     u = crowd ? dw*dh : dw*dh + gw*gh - i; iou = i/u.
+ *   For every threshold t and area range a (area_rng[a] = {lo, hi}; a gt is ignored when crowd or garea < lo or > hi) the
+ *   detections are visited in rank order, each starting from best = min(iou_thrs[t], 1 - 1e-10): first the gts that are not
+ *   ignored and not yet matched at (t, a), in order, taking a gt unless iou < best (ties go to the later gt); only if that
+ *   found nothing, the ignored gts the same way, where a crowd gt may be taken any number of times.
+ *   codes[a][d] (d = row of dbox, n_det words per a) holds ten 2-bit codes, threshold t in bits 2t, 2t+1:
+ *     0 unmatched (false positive), 1 matched to a counted gt, 2 unmatched with dw*dh outside area_rng[a] (ignored),
+ *     3 matched to an ignored gt (ignored).
+ *   npig[cell][a] = number of gts of the cell that are not ignored in a.  A cell of more than 256 gts keeps its "matched"
+ *   bits in `workspace` (y4_coco_workspace(n_cells, longest gt segment) bytes; 0 and NULL allowed below that).
+ *   Errors before any launch: a NULL pointer Y4_ERR_NULL; n_det, n_gt or n_cells < 0, offsets that do not start at 0, decrease,
+ *   end elsewhere than n_det / n_gt, or a cell of more than 100 detections Y4_ERR_SHAPE; workspace too small Y4_ERR_WORKSPACE.
+ *
+ * y4_coco_accumulate_f64: order[cat_off[k] .. cat_off[k + 1]) lists category k's rows of dbox by score descending (ties: by
+ *   row), rank[d] is row d's rank in its cell, npig_cat[k][a] the sum of npig over k's cells.  For every (k, a, m, t), over
+ *   the listed rows with rank < max_dets[m], with integer running counts tp (code 1) and fp (code 0):
+ *     rc[i] = tp[i] / npig, pr[i] = tp[i] / (fp[i] + tp[i] + 2^-52), pr made non-increasing from the right,
+ *     precision[t][r][k][a][m] = pr[first i with rc[i] >= rec_thrs[r]] or 0, recall[t][k][a][m] = rc[last] or 0 without rows;
+ *   npig_cat[k][a] == 0 gives -1 everywhere.  Every entry of both arrays is written; each is one fp64 quotient of integers,
+ *   so nothing depends on the grid.  No floating-point atomics.
+ *   Errors before any launch: NULL pointer Y4_ERR_NULL; n_det or n_cat < 0, a negative max_dets entry, offsets as above
+ *   Y4_ERR_SHAPE. */
+size_t y4_coco_workspace(int n_cells, int max_gts_per_cell);
+int y4_coco_match_f64(const double* dbox /* [n_det][4] */, const int* det_off_dev, const int* det_off_host /* [n_cells+1] */,
+                      int n_det, const double* gbox /* [n_gt][4] */, const double* garea, const int* gcrowd,
+                      const int* gt_off_dev, const int* gt_off_host /* [n_cells+1] */, int n_gt, int n_cells,
+                      const double* iou_thrs /* [10] */, const double* area_rng /* [4][2] */,
+                      unsigned int* codes /* [4][n_det] */, int* npig /* [n_cells][4] */, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int y4_coco_accumulate_f64(const unsigned int* codes, const unsigned char* rank /* [n_det] */, const int* order /* [n_det] */,
+                           int n_det, const int* cat_off_dev, const int* cat_off_host /* [n_cat+1] */,
+                           const long long* npig_cat /* [n_cat][4] */, int n_cat, const double* rec_thrs /* [101] */,
+                           const int* max_dets_host /* [3] */, double* precision /* [10][101][n_cat][4][3] */,
+                           double* recall /* [10][n_cat][4][3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,8 +114,10 @@ PROTOTYPES = {
     'y4_ce_smooth_fwd_f32': (I, [P, I, P, I, I, c_double, P, P, P]),
     'y4_ce_smooth_bwd_f32': (I, [P, I, P, P, P, P, I, I, I, c_double, P]),
     'y4_topk_correct_f32': (I, [P, I, P, I, I, P, I, P, P, P]),
+    'y4_coco_workspace': (Z, [I, I]),
+    'y4_coco_match_f64': (I, [P, P, P, I, P, P, P, P, P, I, I, P, P, P, P, P, Z, P]),
+    'y4_coco_accumulate_f64': (I, [P, P, P, I, P, P, P, I, P, P, P, P, P]),
 }
-
 
 
 class AugSrc(ctypes.Structure):

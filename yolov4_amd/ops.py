@@ -1750,3 +1750,72 @@ def topk_correct(logits, target, ks, want_rank=False):
     check(L.y4_topk_correct_f32(_ptr(logits), ldl, _ptr(target), B, N, int_array(ks), len(ks), _ptr(correct), _ptr(rank),
                                 _stream()), 'topk_correct')
     return (correct, rank) if want_rank else correct
+
+
+# ---------------------------------------------------------------------------------------------- COCO bbox evaluation
+
+def _coco_dev(t, dtype, what):
+    """contiguous device tensor of `dtype`; an empty one is replaced by one element (the ABI takes no NULL)"""
+    if not t.is_cuda:
+        raise Y4Error(f'{what}: tensor is on {t.device}; the yolov4_amd hot path runs on an MI355X only (no CPU fallback)')
+    if t.dtype != dtype:
+        raise Y4Error(f'{what}: expected {dtype}, got {t.dtype}')
+    return t.contiguous() if t.numel() else torch.zeros((1,), device=t.device, dtype=dtype)
+
+
+def _coco_host(a, n, what):
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if a.shape != (n,):
+        raise Y4Error(f'{what}: expected {n} host ints, got shape {a.shape}')
+    return a
+
+
+def coco_match(dbox, det_off, det_off_host, gbox, garea, gcrowd, gt_off, gt_off_host, iou_thrs, area_rng):
+    """y4_coco_match_f64 on CSR cells (include/yolov4_amd.h).  dbox [n_det,4] / gbox [n_gt,4] / garea fp64, gcrowd and the
+    offsets int32 on the device, *_host the offsets as numpy int32.  -> (codes uint32-as-int32 [4, n_det], npig int32
+    [n_cells, 4]).  No host sync."""
+    L = lib()
+    n_cells = int(det_off.numel()) - 1
+    n_det, n_gt = int(dbox.shape[0]), int(gbox.shape[0])
+    dev = dbox.device
+    f64, i32 = torch.float64, torch.int32
+    doh, goh = _coco_host(det_off_host, n_cells + 1, 'coco det_off_host'), _coco_host(gt_off_host, n_cells + 1, 'coco gt_off_host')
+    ins = [_coco_dev(dbox, f64, 'coco dbox'), _coco_dev(det_off, i32, 'coco det_off'), _coco_dev(gbox, f64, 'coco gbox'),
+           _coco_dev(garea, f64, 'coco garea'), _coco_dev(gcrowd, i32, 'coco gcrowd'), _coco_dev(gt_off, i32, 'coco gt_off'),
+           _coco_dev(iou_thrs, f64, 'coco iou_thrs'), _coco_dev(area_rng, f64, 'coco area_rng')]
+    if gt_off.numel() != n_cells + 1 or iou_thrs.numel() != 10 or area_rng.numel() != 8:
+        raise Y4Error('coco_match: offsets of different lengths, or threshold tables not [10] and [4,2]')
+    codes = torch.zeros((4, max(n_det, 1)), device=dev, dtype=i32)
+    npig = torch.zeros((max(n_cells, 1), 4), device=dev, dtype=i32)
+    longest = int((goh[1:] - goh[:-1]).max()) if n_cells > 0 else 0
+    nbytes = int(L.y4_coco_workspace(n_cells, longest))
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None
+    check(L.y4_coco_match_f64(_ptr(ins[0]), _ptr(ins[1]), doh.ctypes.data, n_det, _ptr(ins[2]), _ptr(ins[3]), _ptr(ins[4]),
+                              _ptr(ins[5]), goh.ctypes.data, n_gt, n_cells, _ptr(ins[6]), _ptr(ins[7]), _ptr(codes), _ptr(npig),
+                              _ptr(ws), nbytes, _stream()), 'coco_match')
+    return codes[:, :n_det], npig[:n_cells]
+
+
+def coco_accumulate(codes, rank, order, cat_off, cat_off_host, npig_cat, rec_thrs, max_dets):
+    """y4_coco_accumulate_f64: codes [4, n_det] as coco_match wrote them, rank uint8 [n_det], order int32 [n_det] (rows by
+    category, then score), cat_off int32 [K+1] (+ the same as numpy), npig_cat int64 [K,4], rec_thrs fp64 [101], max_dets three
+    ints.  -> (precision [10,101,K,4,3], recall [10,K,4,3]) fp64 on the device.  No host sync."""
+    L = lib()
+    n_det, K = int(order.numel()), int(cat_off.numel()) - 1
+    dev = cat_off.device
+    coh = _coco_host(cat_off_host, K + 1, 'coco cat_off_host')
+    if codes.dim() != 2 or codes.shape[0] != 4 or codes.shape[1] != n_det or rank.numel() != n_det or rec_thrs.numel() != 101 \
+            or npig_cat.numel() != 4 * K or len(max_dets) != 3:
+        raise Y4Error('coco_accumulate: inconsistent shapes')
+    ins = [_coco_dev(codes, torch.int32, 'coco codes'), _coco_dev(rank, torch.uint8, 'coco rank'),
+           _coco_dev(order, torch.int32, 'coco order'), _coco_dev(cat_off, torch.int32, 'coco cat_off'),
+           _coco_dev(npig_cat, torch.int64, 'coco npig_cat'), _coco_dev(rec_thrs, torch.float64, 'coco rec_thrs')]
+    precision = torch.empty((10, 101, K, 4, 3), device=dev, dtype=torch.float64)
+    recall = torch.empty((10, K, 4, 3), device=dev, dtype=torch.float64)
+    if K == 0:
+        return precision, recall
+    check(L.y4_coco_accumulate_f64(_ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), n_det, _ptr(ins[3]), coh.ctypes.data, _ptr(ins[4]), K,
+                                   _ptr(ins[5]), int_array([int(v) for v in max_dets]), _ptr(precision), _ptr(recall),
+                                   _stream()), 'coco_accumulate')
+    return precision, recall

@@ -120,7 +120,8 @@ def _img_infos(info, batch):
 def validate(val_loader, model, conf_threshold, nms_threshold, device=None, evaluator=None, num_classes=80):
     """build.py:111-190.  Returns (AP50_95, AP50) from `evaluator(records, image_ids)` when one is given (the
     reference calls pycocotools' COCOeval there); without one returns (0, 0) like the reference's empty branch and
-    leaves the COCO-format records on `validate.records`.  Unlike the reference the loader may hand batches larger
+    leaves the COCO-format records on `validate.records`.  `yolo/util/cocoeval.py::COCOEvaluator(annotations)` is such an
+    evaluator: the COCOeval protocol on the device.  Unlike the reference the loader may hand batches larger
     than 1: target['img_info'] is then a list of per-image [h, w, S, S, id, ...] rows."""
     model.eval()
     ids, data_list = [], []
