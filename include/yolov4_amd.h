@@ -363,7 +363,8 @@ int y4_yolo_decode_bwd_f32(const float* logits, int ldl, const float* g_output, 
  *   obj_mask [B,A,F,F] fp32, pos_index [B,A,F,F] int32 (-1 or index into pos_rec),
  *   pos_rec [B,K,8+ceil(C/32)] (x,y,w,h targets, scale, cell, class bitmask), npos [B],
  *   loss_parts[4] doubles (xy, wh, obj, cls), deterministic two-stage reduction.
- * workspace: y4_yolo_loss_workspace() bytes.
+ * workspace: y4_yolo_loss_workspace() bytes.  Its last array, pos_box [B,K,4], holds per record the truth box
+ * (xc,yc,w,h) = label / stride of the last label that hit the cell, for y4_yolo_box_loss_*_f32 below.
  */
 size_t y4_yolo_loss_workspace(int B, int F, int A, int K, int n_classes);
 int y4_yolo_loss_fwd_f32(const float* output, const float* pred, const float* labels, int K,
@@ -386,6 +387,29 @@ int y4_yolo_loss_mask_output_f32(float* output, const float* obj_mask, int B, in
 int y4_yolo_loss_dense_targets_f32(float* target, float* tgt_mask, float* tgt_scale,
                                    int B, int F, int A, int K, int n_classes,
                                    const void* workspace, size_t workspace_bytes, void* stream);
+
+/* IoU-family box regression on the positive records of the workspace that y4_yolo_loss_fwd_f32 filled (call it first,
+ * same B, F, A, K, n_classes).  box_kind: Y4_BOX_IOU | Y4_BOX_GIOU | Y4_BOX_DIOU | Y4_BOX_CIOU.  Per record, in grid
+ * units: p = pred[b,a,j,i,:] (xc,yc,w,h), t = label / stride of the LAST label that hit the cell (stored by the assign
+ * kernels beside the record); eps = 1e-7f; X = IoU, GIoU, DIoU or CIoU of (p, t) (CIoU's alpha = v / (1 - iou + v + eps)
+ * is a constant in the backward).  A NaN anywhere in p makes the record's loss and gradient NaN.
+ *   fwd: loss_parts[0] = gain * sum over records of (1 - X), loss_parts[1] = 0; parts 2 and 3 are left as they are.
+ *        One block, fixed summation order: two calls give the same bits.
+ *   bwd: overwrites channels 0..3 of every positive cell of g_output (dense [B,A,F,F,5+C], already filled by
+ *        y4_yolo_loss_bwd_f32) with (*gscale) * gain * (dL/dpx, dL/dpy, dL/dpw * pw, dL/dph * ph): the gradient wrt the
+ *        train-mode `output`, whose w / h channels are the raw logits.  The box is read from `pred`, never from `output`
+ *        (which y4_yolo_loss_mask_output_f32 may have scaled).  Nothing else of g_output is touched.
+ * Errors before any launch: NULL pointer Y4_ERR_NULL; B, F, A, K, n_classes out of range or an unknown box_kind
+ * Y4_ERR_SHAPE; workspace_bytes < y4_yolo_loss_workspace() Y4_ERR_WORKSPACE. */
+#define Y4_BOX_IOU 1
+#define Y4_BOX_GIOU 2
+#define Y4_BOX_DIOU 3
+#define Y4_BOX_CIOU 4
+int y4_yolo_box_loss_fwd_f32(const float* pred, int box_kind, float gain, int B, int F, int A, int K, int n_classes,
+                             double* loss_parts, const void* workspace, size_t workspace_bytes, void* stream);
+int y4_yolo_box_loss_bwd_f32(const float* pred, int box_kind, float gain, const float* gscale, float* g_output,
+                             int B, int F, int A, int K, int n_classes,
+                             const void* workspace, size_t workspace_bytes, void* stream);
 
 /* Device-side prefix sums of postprocess (no host round trip between its stages):
  * y4_post_scan_i32: seg_offsets[0..n_segments] = exclusive scan of the candidate counts, clamped to `cap` (the capacity, in

@@ -83,6 +83,8 @@ PROTOTYPES = {
     'y4_yolo_loss_bwd_f32': (I, [P, I, P, P, P, I, I, I, I, I, P, Z, P]),
     'y4_yolo_loss_mask_output_f32': (I, [P, P, I, I, I, I, I, P, Z, P]),
     'y4_yolo_loss_dense_targets_f32': (I, [P, P, P, I, I, I, I, I, P, Z, P]),
+    'y4_yolo_box_loss_fwd_f32': (I, [P, I, F, I, I, I, I, I, P, P, Z, P]),
+    'y4_yolo_box_loss_bwd_f32': (I, [P, I, F, P, P, I, I, I, I, I, P, Z, P]),
     'y4_post_count_f32': (I, [P, I, L, I, F, I, P, P]),
     'y4_post_scan_i32': (I, [P, I, L, P, P, P]),
     'y4_post_compact_f32': (I, [P, P, P, I, I, P, P, P, P]),

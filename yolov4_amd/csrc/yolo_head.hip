@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256) void bboxes_iou_kernel(const float* __restrict
 
 // ------------------------------------------------------------------------------------ loss
 struct LossWs {
-    size_t nlabel, npos, truth, pos_cell, pos_val, pos_cls, pos_index, partials, total;
+    size_t nlabel, npos, truth, pos_cell, pos_val, pos_cls, pos_index, partials, pos_box, total;
     int cw, nblocks;
 };
 static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -258,6 +258,7 @@ static LossWs loss_ws(int B, int F, int A, int K, int C) {
     w.pos_cls = o; o = al16(o + (size_t)B * K * w.cw * 4);
     w.pos_index = o; o = al16(o + (size_t)cells * 4);
     w.partials = o; o = al16(o + (size_t)w.nblocks * 4 * 8);
+    w.pos_box = o; o = al16(o + (size_t)B * K * 4 * 4);       // appended: every offset above is what it was without it
     w.total = o;
     return w;
 }
@@ -265,6 +266,7 @@ static LossWs loss_ws(int B, int F, int A, int K, int C) {
 struct LossPtrs {
     int* nlabel; int* npos; float* truth; int* pos_cell; float* pos_val; unsigned* pos_cls; int* pos_index;
     double* partials;
+    float* pos_box;                                            // [B, K, 4]: a record's truth box (xc, yc, w, h), grid units
 };
 static LossPtrs loss_ptrs(const void* ws, const LossWs& l) {
     char* b = static_cast<char*>(const_cast<void*>(ws));
@@ -277,6 +279,7 @@ static LossPtrs loss_ptrs(const void* ws, const LossWs& l) {
     p.pos_cls = reinterpret_cast<unsigned*>(b + l.pos_cls);
     p.pos_index = reinterpret_cast<int*>(b + l.pos_index);
     p.partials = reinterpret_cast<double*>(b + l.partials);
+    p.pos_box = reinterpret_cast<float*>(b + l.pos_box);
     return p;
 }
 
@@ -335,6 +338,8 @@ __global__ void yolo_assign_kernel(const float* __restrict__ labels, int K, int 
         pv[2] = logf(tw / masked.w[a] + 1e-16f);
         pv[3] = logf(th / masked.h[a] + 1e-16f);
         pv[4] = sqrtf(2.0f - tw * th / Ff / Ff);
+        float* pb = w.pos_box + ((long long)b * K + rec) * 4;                // last writer wins, like pv
+        pb[0] = tx; pb[1] = ty; pb[2] = tw; pb[3] = th;
         const int cls = (int)(short)(int)lab[t * 5 + 4];
         if (cls >= 0 && cls < C) w.pos_cls[((long long)b * K + rec) * cw + (cls >> 5)] |= 1u << (cls & 31);
     }
@@ -411,6 +416,8 @@ __global__ __launch_bounds__(64) void yolo_assign_wave_kernel(const float* __res
         pv[2] = logf(tw / masked.w[a] + 1e-16f);
         pv[3] = logf(th / masked.h[a] + 1e-16f);
         pv[4] = sqrtf(2.0f - tw * th / Ff / Ff);
+        float* pb = w.pos_box + ((long long)b * K + rec) * 4;
+        pb[0] = tx; pb[1] = ty; pb[2] = tw; pb[3] = th;
     }
     if (t == 0) w.npos[b] = __popcll(om);
 }
@@ -584,6 +591,153 @@ __global__ void yolo_dense_targets_kernel(float* __restrict__ target, float* __r
     for (int k = 0; k < 4 + C; ++k) tm[k] = 1.f;
     tgt_scale[cell * 2] = pv[4];
     tgt_scale[cell * 2 + 1] = pv[4];
+}
+
+// ------------------------------------------------------------------------------------ IoU-family box loss
+// 1 - X over the positive records, X = IoU | GIoU | DIoU | CIoU of the decoded box p = pred[cell] against the record's
+// truth box (pos_box), both as (xc, yc, w, h) in grid units.  Centres come in relative to the cell origin (px - i and
+// tx - i are exact in fp32: px in [i, i + 1], i = trunc(tx)), so the corner differences do not cancel against the grid
+// offset.  Ties: a corner of p counts as the selected one of min / max only under a strict inequality, the clamp of the
+// intersection passes a gradient only when the raw extent is > 0.  CIoU's alpha is a constant in the gradient.
+// fmaxf / fminf drop NaN operands: a NaN in p is carried to the result explicitly.
+constexpr float BOX_EPS = 1e-7f;
+
+struct BoxTerm { float loss, g0, g1, g2, g3; };                // g: d loss / d(px, py, log pw, log ph)
+
+template <bool GRAD>
+__device__ __forceinline__ BoxTerm box_term(int kind, float px, float py, float pw, float ph, float tx, float ty,
+                                            float tw, float th) {
+    const float pl = px - pw / 2.f, pr = px + pw / 2.f, pt = py - ph / 2.f, pb = py + ph / 2.f;
+    const float tl = tx - tw / 2.f, tr = tx + tw / 2.f, tt = ty - th / 2.f, tb = ty + th / 2.f;
+    const float iwr = fminf(pr, tr) - fmaxf(pl, tl), ihr = fminf(pb, tb) - fmaxf(pt, tt);
+    const float iw = fmaxf(0.f, iwr), ih = fmaxf(0.f, ihr);
+    const float inter = iw * ih;
+    const float uni = ((pw * ph + tw * th) - inter) + BOX_EPS;
+    const float iou = inter / uni;
+    float x = iou;
+    float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;              // d X / d(px, py, pw, ph)
+    float dU0 = 0.f, dU1 = 0.f, dU2 = 0.f, dU3 = 0.f;
+    if (GRAD) {
+        const float ar = (pr < tr && iwr > 0.f) ? 1.f : 0.f, al = (pl > tl && iwr > 0.f) ? 1.f : 0.f;
+        const float ab = (pb < tb && ihr > 0.f) ? 1.f : 0.f, at = (pt > tt && ihr > 0.f) ? 1.f : 0.f;
+        const float dI0 = ih * (ar - al), dI1 = iw * (ab - at);
+        const float dI2 = ih * ((ar + al) / 2.f), dI3 = iw * ((ab + at) / 2.f);
+        dU0 = -dI0; dU1 = -dI1; dU2 = ph - dI2; dU3 = pw - dI3;
+        d0 = (dI0 - iou * dU0) / uni; d1 = (dI1 - iou * dU1) / uni;
+        d2 = (dI2 - iou * dU2) / uni; d3 = (dI3 - iou * dU3) / uni;
+    }
+    if (kind != Y4_BOX_IOU) {
+        const float cw = fmaxf(pr, tr) - fminf(pl, tl), ch = fmaxf(pb, tb) - fminf(pt, tt);
+        float dcw0 = 0.f, dcw2 = 0.f, dch1 = 0.f, dch3 = 0.f;
+        if (GRAD) {
+            const float cr = pr > tr ? 1.f : 0.f, cl = pl < tl ? 1.f : 0.f;
+            const float cb = pb > tb ? 1.f : 0.f, ct = pt < tt ? 1.f : 0.f;
+            dcw0 = cr - cl; dcw2 = (cr + cl) / 2.f;
+            dch1 = cb - ct; dch3 = (cb + ct) / 2.f;
+        }
+        if (kind == Y4_BOX_GIOU) {
+            const float ca = cw * ch + BOX_EPS;
+            x = iou - (ca - uni) / ca;
+            if (GRAD) {
+                const float ca2 = ca * ca;
+                d0 = (d0 + dU0 / ca) - uni * (ch * dcw0) / ca2;
+                d1 = (d1 + dU1 / ca) - uni * (cw * dch1) / ca2;
+                d2 = (d2 + dU2 / ca) - uni * (ch * dcw2) / ca2;
+                d3 = (d3 + dU3 / ca) - uni * (cw * dch3) / ca2;
+            }
+        } else {
+            const float c2 = (cw * cw + ch * ch) + BOX_EPS;
+            const float ex = px - tx, ey = py - ty;
+            const float rho2 = ex * ex + ey * ey;
+            x = iou - rho2 / c2;
+            if (GRAD) {
+                const float c4 = c2 * c2;
+                d0 = d0 - ((2.f * ex) * c2 - rho2 * ((2.f * cw) * dcw0)) / c4;
+                d1 = d1 - ((2.f * ey) * c2 - rho2 * ((2.f * ch) * dch1)) / c4;
+                d2 = d2 + (rho2 * ((2.f * cw) * dcw2)) / c4;
+                d3 = d3 + (rho2 * ((2.f * ch) * dch3)) / c4;
+            }
+            if (kind == Y4_BOX_CIOU) {
+                const float phe = ph + BOX_EPS;
+                const float da = atanf(tw / (th + BOX_EPS)) - atanf(pw / phe);
+                const float v = (0.40528473456935109f * da) * da;          // 4 / pi^2
+                const float alpha = v / (((1.f - iou) + v) + BOX_EPS);
+                x = x - alpha * v;
+                if (GRAD) {
+                    const float den = phe * phe + pw * pw;
+                    const float k = 0.81056946913870217f * da;            // 8 / pi^2
+                    d2 = d2 + alpha * ((k * phe) / den);
+                    d3 = d3 - alpha * ((k * pw) / den);
+                }
+            }
+        }
+    }
+    BoxTerm r;
+    r.loss = 1.f - x;
+    r.g0 = -d0; r.g1 = -d1; r.g2 = -(d2 * pw); r.g3 = -(d3 * ph);
+    if (px != px || py != py || pw != pw || ph != ph) { r.loss = NAN; r.g0 = NAN; r.g1 = NAN; r.g2 = NAN; r.g3 = NAN; }
+    return r;
+}
+
+// the boxes of record slot s = b * K + rec; false for an empty slot
+__device__ __forceinline__ bool box_record(const float* __restrict__ pred, int F, int A, int K, const LossPtrs& w,
+                                           long long s, long long& cell_out, float* p, float* t) {
+    const int b = (int)(s / K), rec = (int)(s - (long long)b * K);
+    if (rec >= w.npos[b]) return false;
+    const int per_img = A * F * F;
+    const int cell = w.pos_cell[s];
+    if (cell < 0 || cell >= per_img) return false;             // never so on a workspace the loss forward filled
+    const int i = cell % F, j = (cell / F) % F;
+    cell_out = (long long)b * per_img + cell;
+    const float* pp = pred + cell_out * 4;
+    const float* tb = w.pos_box + s * 4;
+    p[0] = pp[0] - (float)i; p[1] = pp[1] - (float)j; p[2] = pp[2]; p[3] = pp[3];
+    t[0] = tb[0] - (float)i; t[1] = tb[1] - (float)j; t[2] = tb[2]; t[3] = tb[3];
+    return true;
+}
+
+// One block: a thread adds its slots in slot order, then wave shuffles, then the 16 wave sums in order through LDS.
+constexpr int BOX_BLOCK = 1024;
+__global__ __launch_bounds__(BOX_BLOCK) void yolo_box_loss_fwd_kernel(const float* __restrict__ pred, int kind, float gain,
+                                                                      int B, int F, int A, int K, LossPtrs w,
+                                                                      double* __restrict__ out) {
+    __shared__ double red[BOX_BLOCK / 64];
+    const long long slots = (long long)B * K;
+    double acc = 0;
+    for (long long s = threadIdx.x; s < slots; s += BOX_BLOCK) {
+        long long cell;
+        float p[4], t[4];
+        if (box_record(pred, F, A, K, w, s, cell, p, t))
+            acc += (double)box_term<false>(kind, p[0], p[1], p[2], p[3], t[0], t[1], t[2], t[3]).loss;
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double v = 0;
+        for (int k = 0; k < BOX_BLOCK / 64; ++k) v += red[k];
+        out[0] = v * (double)gain;
+        out[1] = 0.0;
+    }
+}
+
+// One thread per record slot: the four box channels of its cell, over what the dense backward wrote there.
+__global__ __launch_bounds__(256) void yolo_box_loss_bwd_kernel(const float* __restrict__ pred, int kind, float gain,
+                                                                const float* __restrict__ gscale_p,
+                                                                float* __restrict__ g_out, int B, int F, int A, int K,
+                                                                int n_ch, LossPtrs w) {
+    const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= (long long)B * K) return;
+    long long cell;
+    float p[4], t[4];
+    if (!box_record(pred, F, A, K, w, s, cell, p, t)) return;
+    const BoxTerm r = box_term<true>(kind, p[0], p[1], p[2], p[3], t[0], t[1], t[2], t[3]);
+    const float gscale = *gscale_p;
+    float* g = g_out + cell * n_ch;
+    g[0] = (r.g0 * gain) * gscale;
+    g[1] = (r.g1 * gain) * gscale;
+    g[2] = (r.g2 * gain) * gscale;
+    g[3] = (r.g3 * gain) * gscale;
 }
 
 // ------------------------------------------------------------------------------------ postprocess
@@ -1180,6 +1334,39 @@ int y4_yolo_loss_dense_targets_f32(float* target, float* tgt_mask, float* tgt_sc
     if (hipMemsetAsync(tgt_scale, 0, cells * 2 * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
     hipLaunchKernelGGL(yolo_dense_targets_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, target, tgt_mask,
                        tgt_scale, B, F, A, K, n_classes, l.cw, w);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+
+static bool box_kind_ok(int kind) { return kind >= Y4_BOX_IOU && kind <= Y4_BOX_CIOU; }
+
+int y4_yolo_box_loss_fwd_f32(const float* pred, int box_kind, float gain, int B, int F, int A, int K, int n_classes,
+                             double* loss_parts, const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pred || !loss_parts || !workspace) return Y4_ERR_NULL;
+    if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0 || (long long)A * F * F >= (1ll << 31) ||
+        !box_kind_ok(box_kind)) return Y4_ERR_SHAPE;
+    const LossWs l = loss_ws(B, F, A, K, n_classes);
+    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
+    const LossPtrs w = loss_ptrs(workspace, l);
+    hipLaunchKernelGGL(yolo_box_loss_fwd_kernel, dim3(1), dim3(BOX_BLOCK), 0, y4_stream(stream), pred, box_kind, gain,
+                       B, F, A, K, w, loss_parts);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+
+int y4_yolo_box_loss_bwd_f32(const float* pred, int box_kind, float gain, const float* gscale, float* g_output,
+                             int B, int F, int A, int K, int n_classes,
+                             const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pred || !gscale || !g_output || !workspace) return Y4_ERR_NULL;
+    if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0 || (long long)A * F * F >= (1ll << 31) ||
+        !box_kind_ok(box_kind)) return Y4_ERR_SHAPE;
+    const LossWs l = loss_ws(B, F, A, K, n_classes);
+    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
+    const LossPtrs w = loss_ptrs(workspace, l);
+    const long long slots = (long long)B * K;
+    if ((slots + 255) / 256 >= (1ll << 31)) return Y4_ERR_SHAPE;
+    hipLaunchKernelGGL(yolo_box_loss_bwd_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, y4_stream(stream),
+                       pred, box_kind, gain, gscale, g_output, B, F, A, K, 5 + n_classes, w);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }

@@ -1561,12 +1561,27 @@ def yolo_decode_eval(logits, anchors_wh, n_classes, stride, out=None, n_total=No
     return out
 
 
+BOX_LOSS_KINDS = {'mse': 0, 'iou': 1, 'giou': 2, 'diou': 3, 'ciou': 4}      # Y4_BOX_* of include/yolov4_amd.h; 0: none
+
+
+def box_loss_kind(name):
+    """The box_kind id of a box-loss name; ValueError for an unknown one (no GPU needed)."""
+    try:
+        return BOX_LOSS_KINDS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f'unknown box_loss {name!r}: expected one of {sorted(BOX_LOSS_KINDS)}') from None
+
+
 class YoloLossLayerFn(torch.autograd.Function):
-    """YOLOLoss.build_target + loss terms for one layer, yolo/model/yololoss.py:118-371,385-432."""
+    """YOLOLoss.build_target + loss terms for one layer, yolo/model/yololoss.py:118-371,385-432.  With
+    cfg['box_loss'] in {'iou', 'giou', 'diou', 'ciou'} the xy / wh terms are replaced by cfg['box_gain'] * sum(1 - X)
+    over the positive records (parts[0]; parts[1] = 0): two more launches on the same workspace."""
 
     @staticmethod
     def forward(ctx, output, pred, labels, cfg):
         L = lib()
+        box_kind = box_loss_kind(cfg.get('box_loss', 'mse'))
+        box_gain = float(cfg.get('box_gain', 1.0))
         _require_gpu(output, 'YOLOLoss output')
         B, A, F, _, n_ch = output.shape
         C = n_ch - 5
@@ -1584,6 +1599,10 @@ class YoloLossLayerFn(torch.autograd.Function):
         check(L.y4_yolo_loss_fwd_f32(_ptr(output), _ptr(pred), _ptr(labels), K, B, F, A, C, float(cfg['stride']),
                                      float(cfg['ignore_thresh']), anchors, len(cfg['all_anchors']), amask,
                                      _ptr(obj_mask), _ptr(parts), _ptr(ws), nbytes, _stream()), 'yolo_loss_fwd')
+        if box_kind:
+            check(L.y4_yolo_box_loss_fwd_f32(_ptr(pred), box_kind, box_gain, B, F, A, K, C, _ptr(parts), _ptr(ws),
+                                             nbytes, _stream()), 'yolo_box_loss_fwd')
+        ctx.box = (box_kind, box_gain, pred if box_kind else None)      # the backward reads the box from pred
         ctx.meta = (B, F, A, K, C, nbytes)
         ctx.ws = ws
         ctx.obj_mask = obj_mask
@@ -1606,6 +1625,10 @@ class YoloLossLayerFn(torch.autograd.Function):
         gs = gloss.detach().to(torch.float32).reshape(1).contiguous()
         check(L.y4_yolo_loss_bwd_f32(_ptr(ctx.output), 1 if ctx.mutate else 0, _ptr(ctx.obj_mask), _ptr(gs), _ptr(g),
                                      B, F, A, K, C, _ptr(ctx.ws), nbytes, _stream()), 'yolo_loss_bwd')
+        box_kind, box_gain, pred = ctx.box
+        if box_kind:
+            check(L.y4_yolo_box_loss_bwd_f32(_ptr(pred), box_kind, box_gain, _ptr(gs), _ptr(g), B, F, A, K, C,
+                                             _ptr(ctx.ws), nbytes, _stream()), 'yolo_box_loss_bwd')
         return g, None, None, None
 
 

@@ -15,4 +15,6 @@ def build_model(args: Namespace, cfg: Dict, device=None):
 
 
 def build_criterion(cfg: Dict, device=None):
-    return YOLOLoss(cfg['MODEL'], ignore_thresh=float(cfg['CRITERION']['IGNORE_THRESH']), device=device).to(device)
+    crit = cfg['CRITERION']
+    return YOLOLoss(cfg['MODEL'], ignore_thresh=float(crit['IGNORE_THRESH']), device=device,
+                    box_loss=crit.get('BOX_LOSS', 'mse'), box_gain=float(crit.get('BOX_LOSS_GAIN', 1.0))).to(device)

@@ -1,7 +1,9 @@
 # -*- coding: utf-8 -*-
 """Detection loss behind the reference's YOLOLoss API (yolo/model/yololoss.py:94-443):
 YOLOv3-style weighted-BCE(xy) + MSE(wh)/2 + BCE(obj) + BCE(cls), summed over batch and
-the 3 layers (no CIoU / focal anywhere in the reference)."""
+the 3 layers (no CIoU / focal anywhere in the reference).  Opt-in beyond the
+reference: box_loss = 'iou' | 'giou' | 'diou' | 'ciou' replaces the xy / wh terms by
+box_gain * sum(1 - X) over the positive cells ("IoU-family box losses")."""
 from typing import Dict
 
 import numpy as np
@@ -20,8 +22,11 @@ def bboxes_iou(bboxes_a, bboxes_b, xyxy=True):
 class YOLOLoss(nn.Module):
     strides = [8, 16, 32]
 
-    def __init__(self, cfg: Dict, ignore_thresh=0.7, device=None, mutate_outputs=True):
+    def __init__(self, cfg: Dict, ignore_thresh=0.7, device=None, mutate_outputs=True, box_loss='mse', box_gain=1.0):
         super().__init__()
+        ops.box_loss_kind(box_loss)                 # ValueError for an unknown name, before anything touches a GPU
+        self.box_loss = box_loss
+        self.box_gain = float(box_gain)
         self.cfg = cfg
         self.ignore_thresh = ignore_thresh
         self.device = device
@@ -36,12 +41,14 @@ class YOLOLoss(nn.Module):
         # anchors / stride in float64, used as fp32 (yololoss.py:155-167)
         grid = [(float(np.float32(w / st)), float(np.float32(h / st))) for w, h in self.anchors]
         return {'stride': st, 'ignore_thresh': float(np.float32(self.ignore_thresh)), 'all_anchors': grid,
-                'anch_mask': list(self.cfg['ANCHOR_MASK'][layer_no]), 'mutate_output': self.mutate_outputs}
+                'anch_mask': list(self.cfg['ANCHOR_MASK'][layer_no]), 'mutate_output': self.mutate_outputs,
+                'box_loss': self.box_loss, 'box_gain': self.box_gain}
 
     def build_target(self, output, pred, layer_no, labels):
         """Dense (target, obj_mask, tgt_mask, tgt_scale) as yololoss.py:118-371 returns them."""
         cfg = self._layer_cfg(layer_no)
         cfg['mutate_output'] = False
+        cfg['box_loss'] = 'mse'                     # the dense targets do not depend on the box loss
         ops.YoloLossLayerFn.apply(output.detach().contiguous(), pred, labels, cfg)
         target, tgt_mask, tgt_scale = ops.yolo_loss_dense_targets(cfg['last'])
         return target, cfg['last']['obj_mask'], tgt_mask, tgt_scale
