@@ -35,6 +35,8 @@ extern "C" {
 #define Y4_ERR_LAUNCH 3     /* hipLaunch / hipMemsetAsync reported an error         */
 #define Y4_ERR_WORKSPACE 4  /* workspace too small                                  */
 #define Y4_ERR_NODEVICE 5   /* no gfx950 device visible                             */
+#define Y4_ERR_FORMAT 6     /* malformed or truncated input data (JPEG)             */
+#define Y4_ERR_UNSUPPORTED 7 /* valid input outside the supported subset (JPEG)     */
 
 /* activation ids: darknet/darknet.py:41-51 ('relu' | 'leaky_relu' (0.1) | 'mish' | 'linear') */
 #define Y4_ACT_LINEAR 0
@@ -657,6 +659,77 @@ int y4_coco_accumulate_f64(const unsigned int* codes, const unsigned char* rank 
                            const long long* npig_cat /* [n_cat][4] */, int n_cat, const double* rec_thrs /* [101] */,
                            const int* max_dets_host /* [3] */, double* precision /* [10][101][n_cat][4][3] */,
                            double* recall /* [10][n_cat][4][3] */, void* stream);
+
+/* ---------------------------------------------------------------- JPEG decoding (what cv2.imread does for the reference's
+ * yolo/data/cocodataset.py:97), split in two: the serial Huffman stage on the host, everything per pixel on the device.
+ *
+ * Supported: Huffman sequential JPEG (SOF0 / SOF1), 8-bit, ONE interleaved scan, 1 component or 3 YCbCr components at 4:4:4,
+ * 4:2:2 (h2v1) or 4:2:0 (h2v2); any number of DQT / DHT segments, 8- or 16-bit quantisation tables, DRI / RSTn; APPn and COM
+ * are skipped, 0xFF fill bytes before markers accepted.  Y4_ERR_UNSUPPORTED: a valid JPEG outside that subset (progressive,
+ * arithmetic, lossless, 12-bit, 4 components, other sampling, several scans, RGB-coded components).  Y4_ERR_FORMAT: truncated
+ * data, a segment length past the end, missing tables, a Huffman code that is not in its table, a zero run past coefficient
+ * 63, a coefficient outside int16, a zero dimension, a wrong RSTn sequence.
+ *
+ * Host stage (no GPU, no threads, no global state; every read checked against nbytes, every write against coef_cap): */
+typedef struct y4_jpeg_info {
+    int width, height;              /* as stored, before the orientation is applied */
+    int ncomp;                      /* 1 or 3 */
+    int hs[3], vs[3];               /* sampling factors (one component: 1, 1; absent components: 0) */
+    int mcus_x, mcus_y;             /* MCU grid: ceil(width / (8 hs[0])) x ceil(height / (8 vs[0])) */
+    int blocks_w[3], blocks_h[3];   /* padded block grid of each component: mcus_x * hs[c], mcus_y * vs[c] */
+    int restart_interval;           /* MCUs between RSTn markers, 0: none */
+    int orientation;                /* EXIF tag 0x0112, 1..8; 1 when absent or unreadable */
+    int reserved;
+    long long coef_count;           /* int16 elements of the coefficient buffer: 64 * sum_c blocks_w[c] * blocks_h[c] */
+} y4_jpeg_info;
+/* y4_jpeg_parse_host fills the record.  y4_jpeg_entropy_host writes the QUANTISED coefficients (not dequantised), in natural
+ * (row-major, de-zigzagged) order, 64 int16 per block, component after component, each component's blocks in raster order
+ * over its padded grid; and qt_host[c] = component c's quantisation table in natural order (zeros for absent components).
+ * Y4_ERR_WORKSPACE when coef_cap < info->coef_count, Y4_ERR_SHAPE when the record does not belong to the data. */
+int y4_jpeg_parse_host(const void* data_host, size_t nbytes, y4_jpeg_info* info_host);
+int y4_jpeg_entropy_host(const void* data_host, size_t nbytes, const y4_jpeg_info* info_host, short* coef_host,
+                         long long coef_cap, unsigned short* qt_host /* [3][64] */);
+
+/* Device stage: one call per BATCH, two launches over all jobs (IDCT into the component planes; upsample, colour-convert,
+ * store).  One record per image: */
+typedef struct y4_jpeg_job {
+    const short* coef;              /* device, 16-byte aligned, info.coef_count elements as the host stage wrote them */
+    void* out;                      /* device, uint8 HWC, 3 channels */
+    long long out_pitch;            /* bytes per output row, >= 3 * output width */
+    long long ws_offset;            /* bytes, multiple of 16: this job's info.coef_count bytes of the workspace (the planes) */
+    y4_jpeg_info info;
+    int apply_orientation;          /* 1: store through the EXIF index map; output is height x width swapped for 5..8 */
+    int swap_rb;                    /* 0: B, G, R in memory (cv2.imread); 1: R, G, B */
+    unsigned short qt[3][64];
+} y4_jpeg_job;
+/* The table is passed twice, like the augmentation tables: jobs_dev is what the kernels read, jobs_host the same bytes in
+ * host memory, checked before anything is launched (the caller copies host -> device on the same stream).
+ * y4_jpeg_workspace: bytes of planes for these images, packed in order with each job rounded up to 16 bytes.
+ *
+ * The arithmetic is libjpeg-turbo's default decompression path, bit for bit:
+ *   1. dequantise (coefficient * table entry, int32) and the "islow" integer IDCT of jidctint: CONST_BITS 13, PASS1_BITS 2,
+ *      constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995 25172; columns first, descaled by 11, then rows,
+ *      descaled by 18 (descale by n: add 1 << (n-1), arithmetic shift right by n); add 128, clamp to 0..255;
+ *      sums and products wrap modulo 2^32 (a forged file can make them; libjpeg gives arbitrary pixels there too);
+ *   2. a chroma plane has dw x dh = ceil(width hs[c] / hs[0]) x ceil(height vs[c] / vs[0]) samples; indices beyond it take
+ *      the last real sample, never the IDCT padding;
+ *      h2v1 "fancy": out[2i] = (3 in[i] + in[i-1] + 1) >> 2, out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2;
+ *      h2v2 "fancy": cs[j] = 3 row[j] + neighbour[j], the neighbour being the row above for the upper output row and the row
+ *      below for the lower one; out[2j] = (3 cs[j] + cs[j-1] + 8) >> 4, out[2j+1] = (3 cs[j] + cs[j+1] + 7) >> 4
+ *      (with the edge replication this gives the copies / the 4 cs forms at the first and last output);
+ *      dw <= 2: plain replication in both directions instead;
+ *   3. cb = Cb - 128, cr = Cr - 128: R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *      G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), each clamped to 0..255; one component: R = G = B = Y;
+ *   4. the pixel of stored position (x, y) goes to (x', y') of the output: orientation 1 (x, y), 2 (W-1-x, y),
+ *      3 (W-1-x, H-1-y), 4 (x, H-1-y), 5 (y, x), 6 (H-1-y, x), 7 (H-1-y, W-1-x), 8 (y, W-1-x); without apply_orientation
+ *      always (x, y).  Bytes between 3 * output width and out_pitch are never written.
+ * Errors before any launch: NULL pointer (a job's coef or out included) Y4_ERR_NULL; n_jobs outside [1, 65535], a record
+ * whose geometry is not what y4_jpeg_parse_host gives for its width, height and sampling, a misaligned coef or ws_offset, a
+ * pitch below 3 * output width or an orientation outside 1..8 Y4_ERR_SHAPE; ws_offset + coef_count beyond workspace_bytes
+ * Y4_ERR_WORKSPACE. */
+size_t y4_jpeg_workspace(const y4_jpeg_info* infos_host, int n);
+int y4_jpeg_decode_u8(const y4_jpeg_job* jobs_dev, const y4_jpeg_job* jobs_host, int n_jobs, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

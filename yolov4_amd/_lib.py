@@ -119,7 +119,13 @@ PROTOTYPES = {
     'y4_coco_workspace': (Z, [I, I]),
     'y4_coco_match_f64': (I, [P, P, P, I, P, P, P, P, P, I, I, P, P, P, P, P, Z, P]),
     'y4_coco_accumulate_f64': (I, [P, P, P, I, P, P, P, I, P, P, P, P, P]),
+    'y4_jpeg_parse_host': (I, [P, Z, P]),
+    'y4_jpeg_entropy_host': (I, [P, Z, P, P, L, P]),
+    'y4_jpeg_workspace': (Z, [P, I]),
+    'y4_jpeg_decode_u8': (I, [P, P, I, P, Z, P]),
 }
+
+ERR_FORMAT, ERR_UNSUPPORTED = 6, 7
 
 
 class AugSrc(ctypes.Structure):
@@ -133,6 +139,19 @@ class AugSrc(ctypes.Structure):
 class AugSample(ctypes.Structure):
     """y4_aug_sample (16 bytes)"""
     _fields_ = [('cut_x', c_int), ('cut_y', c_int), ('n_src', c_int), ('first', c_int)]
+
+
+class JpegInfo(ctypes.Structure):
+    """y4_jpeg_info (88 bytes)"""
+    _fields_ = [('width', c_int), ('height', c_int), ('ncomp', c_int), ('hs', c_int * 3), ('vs', c_int * 3),
+                ('mcus_x', c_int), ('mcus_y', c_int), ('blocks_w', c_int * 3), ('blocks_h', c_int * 3),
+                ('restart_interval', c_int), ('orientation', c_int), ('reserved', c_int), ('coef_count', c_longlong)]
+
+
+class JpegJob(ctypes.Structure):
+    """y4_jpeg_job (512 bytes)"""
+    _fields_ = [('coef', c_void_p), ('out', c_void_p), ('out_pitch', c_longlong), ('ws_offset', c_longlong),
+                ('info', JpegInfo), ('apply_orientation', c_int), ('swap_rb', c_int), ('qt', (ctypes.c_uint16 * 64) * 3)]
 
 
 _lib = None

@@ -12,6 +12,8 @@ const char* y4_strerror(int code) {
         case Y4_ERR_LAUNCH: return "HIP launch failed";
         case Y4_ERR_WORKSPACE: return "workspace too small";
         case Y4_ERR_NODEVICE: return "no gfx950 device";
+        case Y4_ERR_FORMAT: return "malformed or truncated data";
+        case Y4_ERR_UNSUPPORTED: return "valid data outside the supported subset";
         default: return "unknown error";
     }
 }

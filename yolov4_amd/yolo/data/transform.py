@@ -11,8 +11,8 @@ Training input pipeline (below `val_batch`): the reference's `Transform._get_tra
 mean fill, flip, float resize, HSV jitter, 4-image mosaic -- split into a host sampler that makes every random draw
 (`sample_train_params` -> `MosaicParams`), fp64 box arithmetic on the host (`transform_boxes`, `mosaic_boxes`) and two HIP
 launches per batch on csrc/augment.hip (`train_batch`).  `Transform` keeps the reference's constructor and call.
-Not here: JPEG decoding and the COCO dataset class (callers hand decoded uint8 BGR arrays), and `resize_and_pad`, which the
-reference's `Transform` never calls.
+JPEG decoding is in `jpeg.py`, the COCO dataset class and the batch loader in `cocodataset.py`.  Not here: `resize_and_pad`,
+which the reference's `Transform` never calls.
 """
 import ctypes
 import random as _random
