@@ -242,6 +242,32 @@ int y4_conv2d_stem_wgrad_f32(const float* x, long long sxb, long long sxc, long 
                              const float* dy, int lddy, float* dw, int B, int H, int W, int Cout,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* Stem conv + training-mode BatchNorm + activation WITHOUT the pre-BatchNorm tensor (csrc/stem_fused.hip): every pass
+ * re-forms y0 = conv(x, w) in registers (the arithmetic of y4_conv2d_stem_fwd_f32 in conv modes 1-3, bit for bit), so
+ * neither y0 nor its gradient is ever stored.  x as in y4_conv2d_stem_fwd_f32 (element strides), w KRSC [Cout][3][3][3].
+ * y4_stem_fused_ok: 1 if the passes can address the problem in the current conv mode (modes 1-3; Cout <= 32, a multiple
+ *   of 4; W >= 5; non-negative strides; the whole of x inside one 32-bit byte window) -- z and dz are windowed per 256-pixel
+ *   group and may be of any size.  Otherwise 0: use the separate conv / BatchNorm calls.
+ * y4_stem_bn_act_fwd_f32: batch statistics (mean, invstd and the running statistics exactly as y4_conv2d_stem_fwd_f32 +
+ *   y4_bn_finalize_partials_f32 leave them; the workspace begins with the same [ceil(B*H*W/256)][2][Cout] partial rows),
+ *   then z[B*H*W][ldz] = act((y0 - mean) * invstd * gamma + beta) and max|z| folded into *out_amax (nullable) as
+ *   y4_bn_act_fwd_f32 does.
+ * y4_stem_bn_act_bwd_f32: dgamma, dbeta as y4_bn_act_bwd_f32 (batch statistics) and dw[Cout][3][3][3] = wgrad(x, dy0) with
+ *   dy0 = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat)), g = dz * act'(gamma * xhat + beta), kept in registers.
+ * All reductions are two-stage and fixed-order (deterministic); workspaces are private to the call in stream order. */
+int y4_stem_fused_ok(long long sxb, long long sxc, long long sxh, long long sxw, int B, int H, int W, int Cout);
+size_t y4_stem_bn_act_fwd_workspace(int B, int H, int W, int Cout);
+int y4_stem_bn_act_fwd_f32(const float* x, long long sxb, long long sxc, long long sxh, long long sxw, const float* w,
+                           int B, int H, int W, int Cout, const float* gamma, const float* beta, int act,
+                           float* mean, float* invstd, float* running_mean, float* running_var, long long* num_batches_tracked,
+                           float momentum, float eps, float* z, int ldz, unsigned* out_amax,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t y4_stem_bn_act_bwd_workspace(int B, int H, int W, int Cout);
+int y4_stem_bn_act_bwd_f32(const float* x, long long sxb, long long sxc, long long sxh, long long sxw, const float* w,
+                           const float* dz, int lddz, const float* mean, const float* invstd, const float* gamma,
+                           const float* beta, int act, int B, int H, int W, int Cout,
+                           float* dgamma, float* dbeta, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------- BatchNorm + activation
  * Replaces nn.BatchNorm2d (training mode: batch statistics, eps 1e-5, momentum 0.1, biased
  * variance for normalisation, unbiased for running_var) + the activation,

@@ -59,6 +59,11 @@ PROTOTYPES = {
     'y4_conv2d_wgrad_f32': (I, [P, I, P, I, P, I, I, I, I, I, I, I, P, Z, P, P, P]),
     'y4_conv2d_stem_wgrad_workspace': (Z, [I, I, I, I]),
     'y4_conv2d_stem_wgrad_f32': (I, [P, L, L, L, L, P, I, P, I, I, I, I, P, Z, P]),
+    'y4_stem_fused_ok': (I, [L, L, L, L, I, I, I, I]),
+    'y4_stem_bn_act_fwd_workspace': (Z, [I, I, I, I]),
+    'y4_stem_bn_act_fwd_f32': (I, [P, L, L, L, L, P, I, I, I, I, P, P, I, P, P, P, P, P, F, F, P, I, P, P, Z, P]),
+    'y4_stem_bn_act_bwd_workspace': (Z, [I, I, I, I]),
+    'y4_stem_bn_act_bwd_f32': (I, [P, L, L, L, L, P, P, I, P, P, P, P, I, I, I, I, I, P, P, P, P, Z, P]),
     'y4_bn_workspace': (Z, [L, I]),
     'y4_bn_finalize_workspace': (Z, [I]),
     'y4_bn_finalize_partials_f32': (I, [P, L, L, I, P, P, P, P, P, F, F, P, Z, P]),

@@ -118,3 +118,64 @@ __device__ __forceinline__ f32x4 y4_buf_load4(__amdgpu_buffer_rsrc_t r, unsigned
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff_bytes, (int)soff_bytes, 0);
     return __builtin_bit_cast(f32x4, v);
 }
+
+// ---- the bf16x3 split (conv_igemm.hip, stem_fused.hip): an fp32 value as the exact sum of three truncated bf16 pieces
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+// pack the upper halves (= truncated bf16) of two fp32 words: result = {hi16(x1), hi16(x0)}
+__device__ __forceinline__ unsigned pack_hi16(unsigned x1, unsigned x0) { return __builtin_amdgcn_perm(x1, x0, 0x07060302u); }
+__device__ __forceinline__ void split3x4(const f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
+    unsigned h1[4], h2[4], h3[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        h1[e] = __float_as_uint(v[e]);
+        const float r1 = v[e] - __uint_as_float(h1[e] & 0xffff0000u);     // exact
+        h2[e] = __float_as_uint(r1);
+        const float r2 = r1 - __uint_as_float(h2[e] & 0xffff0000u);       // exact, <= 8 significant bits left
+        h3[e] = __float_as_uint(r2);
+    }
+    p1[0] = pack_hi16(h1[1], h1[0]); p1[1] = pack_hi16(h1[3], h1[2]);
+    p2[0] = pack_hi16(h2[1], h2[0]); p2[1] = pack_hi16(h2[3], h2[2]);
+    p3[0] = pack_hi16(h3[1], h3[0]); p3[1] = pack_hi16(h3[3], h3[2]);
+}
+
+// ---- optional by-product of the sweeps that PRODUCE a conv operand (pointwise.hip, stem_fused.hip): bit pattern of
+// max|finite output| folded into *out with an integer atomicMax (order independent); conv mode 3 ("f16x2") scales its
+// operands by it
+__device__ __forceinline__ void amax_track1(unsigned& m, const float o) {
+    const unsigned b = __float_as_uint(o) & 0x7fffffffu;
+    if (b < 0x7f800000u && b > m) m = b;
+}
+__device__ __forceinline__ void amax_track(unsigned& m, const f32x4 o) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) amax_track1(m, o[e]);
+}
+// (blocks of 256 threads, every thread calls it)
+__device__ __forceinline__ void amax_commit(unsigned m, unsigned* out) {
+    // waves folded through LDS, ONE atomic per block, and only when it would raise the word (it only grows; a stale
+    // read merely costs an atomic).  Per-wave atomics on one address serialised: +150 us per BatchNorm sweep, measured.
+    __shared__ unsigned wmax[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned o = (unsigned)__shfl_xor((int)m, off, 64);
+        m = o > m ? o : m;
+    }
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned v = wmax[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w) v = wmax[w] > v ? wmax[w] : v;
+        if (v > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, v);
+    }
+}
+
+// ---- host-side pieces other translation units launch for stem_fused.hip
+namespace y4 {
+// pointwise.hip: per-block rows part[nparts][2][C] of (sum g, sum g xhat) -> dbeta, dgamma and the fp64 words acc[2C] at the
+// head of `workspace` (y4_bn_finalize_workspace(C) bytes), fixed order
+int bn_bwd_fold_finalize(const float* part, long long nparts, long long M, int C, void* workspace, float* dgamma, float* dbeta,
+                         const float* gamma, const float* invstd, hipStream_t st);
+// conv_igemm.hip: per-wave slabs [nslabs][32 n][32 j] -> dw[Cout][27] through part[64][1024] doubles, fixed order
+int stem_wgrad_fold(const float* slabs, int nslabs, double* part, float* dw, int Cout, hipStream_t st);
+}  // namespace y4

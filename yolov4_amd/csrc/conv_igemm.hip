@@ -292,11 +292,7 @@ __global__ __launch_bounds__(256, (BKT == 16 ? 3 : 2)) void conv_gather_mfma_f32
 // at 6/16 of the fp32-MFMA cost.  Same tiling / gather / epilogues as conv_gather_mfma_f32.
 // LDS: 3 planes x [rows][32 + 8] bf16 per operand (80-B pitch: conflict-free ds_read_b128), single stage,
 // register prefetch of the next K-tile under the MFMAs.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-// pack the upper halves (= truncated bf16) of two fp32 words: result = {hi16(x1), hi16(x0)}
-__device__ __forceinline__ unsigned pack_hi16(unsigned x1, unsigned x0) { return __builtin_amdgcn_perm(x1, x0, 0x07060302u); }
+// (bf16x8, u32x2, pack_hi16 and split3x4 -- the exact three-piece truncation split -- live in common.h)
 
 // round-to-nearest-even bf16 of 4 floats, packed (plain-bf16 mode: one plane, one MFMA per product)
 __device__ __forceinline__ unsigned rn_bf16_bits(float x) {
@@ -308,21 +304,6 @@ __device__ __forceinline__ u32x2 round1x4(const f32x4 v) {
     p[0] = pack_hi16(rn_bf16_bits(v[1]), rn_bf16_bits(v[0]));
     p[1] = pack_hi16(rn_bf16_bits(v[3]), rn_bf16_bits(v[2]));
     return p;
-}
-
-__device__ __forceinline__ void split3x4(const f32x4 v, u32x2& p1, u32x2& p2, u32x2& p3) {
-    unsigned h1[4], h2[4], h3[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        h1[e] = __float_as_uint(v[e]);
-        const float r1 = v[e] - __uint_as_float(h1[e] & 0xffff0000u);     // exact
-        h2[e] = __float_as_uint(r1);
-        const float r2 = r1 - __uint_as_float(h2[e] & 0xffff0000u);       // exact, <= 8 significant bits left
-        h3[e] = __float_as_uint(r2);
-    }
-    p1[0] = pack_hi16(h1[1], h1[0]); p1[1] = pack_hi16(h1[3], h1[2]);
-    p2[0] = pack_hi16(h2[1], h2[0]); p2[1] = pack_hi16(h2[3], h2[2]);
-    p3[0] = pack_hi16(h3[1], h3[0]); p3[1] = pack_hi16(h3[3], h3[2]);
 }
 
 template <int BM, int BN, int WM, int WN, bool TRANSPOSED, int NP = 3>
@@ -1715,6 +1696,14 @@ constexpr int STEM_WAVES = 4096;
 }  // namespace
 
 namespace y4 {
+// the two fold launches of y4_conv2d_stem_wgrad_f32 over another producer's slabs (stem_fused.hip)
+int stem_wgrad_fold(const float* slabs, int nslabs, double* part, float* dw, int Cout, hipStream_t st) {
+    hipLaunchKernelGGL(stem_wgrad_reduce1_kernel, dim3(64), dim3(256), 0, st, slabs, part, nslabs);
+    Y4_CHECK_LAUNCH();
+    hipLaunchKernelGGL(stem_wgrad_reduce2_kernel, dim3(1), dim3(256), 0, st, part, dw, 64, Cout);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
 int slab_reduce(const float* slabs, float* dw, long long n, int splits, hipStream_t st) {
     if ((n & 3) == 0 && !(reinterpret_cast<uintptr_t>(dw) & 15) && !(reinterpret_cast<uintptr_t>(slabs) & 15)) {
         const long long nvec = n / 4;

@@ -193,33 +193,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(const double* __restri
     }
 }
 
-// optional by-product of the sweeps that PRODUCE a conv operand: bit pattern of max|finite output| folded into *out
-// with an integer atomicMax (order independent); conv mode 3 ("f16x2") scales its operands by it
-__device__ __forceinline__ void amax_track(unsigned& m, const f32x4 o) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const unsigned b = __float_as_uint(o[e]) & 0x7fffffffu;
-        if (b < 0x7f800000u && b > m) m = b;
-    }
-}
-__device__ __forceinline__ void amax_commit(unsigned m, unsigned* out) {
-    // waves folded through LDS, ONE atomic per block, and only when it would raise the word (it only grows; a stale
-    // read merely costs an atomic).  Per-wave atomics on one address serialised: +150 us per BatchNorm sweep, measured.
-    __shared__ unsigned wmax[PW_THREADS / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned o = (unsigned)__shfl_xor((int)m, off, 64);
-        m = o > m ? o : m;
-    }
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned v = wmax[0];
-#pragma unroll
-        for (int w = 1; w < PW_THREADS / 64; ++w) v = wmax[w] > v ? wmax[w] : v;
-        if (v > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, v);
-    }
-}
+// (amax_track / amax_commit -- max|finite output| as a by-product of the sweeps that produce a conv operand -- live in common.h)
 
 // Upper bound of max|z|, z = act(gamma xhat + beta) (+ residual), WITHOUT a pass over the data: a sample of M values with
 // mean mu and (biased) variance var has max|y - mu| <= sqrt((M - 1) var), so |xhat| <= sqrt(M - 1); |act(v)| <= |v| for
@@ -1280,3 +1254,20 @@ int y4_act_bwd_f32(const float* x, const float* dy, float* dx, long long n, int 
 }
 
 }  // extern "C"
+
+namespace y4 {
+// stages 2 and 3 of the BatchNorm backward reduction for a caller with its own reduce pass (stem_fused.hip): the same fold and
+// finalize launches as bn_act_bwd_impl (workspace head: acc[2C] | bacc[FOLD_BLOCKS][2C] doubles)
+int bn_bwd_fold_finalize(const float* part, long long nparts, long long M, int C, void* workspace, float* dgamma, float* dbeta,
+                         const float* gamma, const float* invstd, hipStream_t st) {
+    double* acc = static_cast<double*>(workspace);
+    double* bacc = acc + 2 * C;
+    int nb = 0;
+    const int rc = fold_partials(part, nparts, C, bacc, &nb, st);
+    if (rc != Y4_OK) return rc;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, st, bacc, nb, C, acc, dgamma, dbeta, gamma,
+                       invstd, 1.0 / (double)M, static_cast<unsigned*>(nullptr));
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+}  // namespace y4

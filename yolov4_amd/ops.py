@@ -368,6 +368,59 @@ def conv_fwd_bnstats_raw(x, w, k, s, running_mean, running_var, nbt, momentum, e
     return y, mean, invstd
 
 
+# ------------------------------------------------------------------ stem without its pre-BatchNorm tensor (csrc/stem_fused.hip)
+def stem_fused_ok(x, Cout, k, s):
+    """The 3 -> Cout 3x3/s1 stem over x can run as the recomputing passes (y4_stem_fused_ok: conv modes 1-3, x inside one
+    32-bit window; z and dz are windowed per group and may be of any size)."""
+    if x.dim() != 4 or x.shape[1] != 3 or k != 3 or s != 1 or x.dtype != torch.float32:
+        return False
+    B, _, H, W = x.shape
+    return bool(lib().y4_stem_fused_ok(*x.stride(), B, H, W, Cout))
+
+
+def stem_bn_act_fwd_raw(x, w, gamma, beta, act, running_mean, running_var, nbt, momentum, eps, out=None, out_amax=None):
+    """Training-mode stem: z = act(BatchNorm(conv(x, w))) in two recomputing passes; returns (z, mean, invstd)."""
+    L = lib()
+    B, _, H, W = x.shape
+    Cout = w.shape[0]
+    z = out if _slot_ok(out, (B, Cout, H, W)) else empty_nhwc(B, Cout, H, W, x.device)
+    mean = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    invstd = torch.empty(Cout, device=x.device, dtype=torch.float32)
+    nbytes = L.y4_stem_bn_act_fwd_workspace(B, H, W, Cout)
+    ws = _ws(nbytes, x.device)
+    check(L.y4_stem_bn_act_fwd_f32(_ptr(x), *x.stride(), _ptr(krsc(w)), B, H, W, Cout, _ptr(gamma), _ptr(beta), ACT_IDS[act],
+                                   _ptr(mean), _ptr(invstd), _ptr(running_mean), _ptr(running_var), _ptr(nbt), float(momentum),
+                                   float(eps), _ptr(z), nhwc_pitch(z), _ptr(out_amax), _ptr(ws), nbytes, _stream()),
+          'stem_bn_act_fwd')
+    return z, mean, invstd
+
+
+def stem_bn_act_bwd_raw(x, w, dz, mean, invstd, gamma, beta, act, dgamma_out=None, dbeta_out=None, dw_out=None):
+    """Backward of stem_bn_act_fwd_raw wrt the filter and the BatchNorm parameters: (dw, dgamma, dbeta).  The *_out
+    destinations (gradient slots of a flat DDP bucket) are written in place when they qualify."""
+    L = lib()
+    B, _, H, W = x.shape
+    Cout = w.shape[0]
+    dz, lddz = as_nhwc(dz, need_vec4=False)
+
+    def slot(t):
+        ok = t is not None and t.dtype == torch.float32 and tuple(t.shape) == (Cout,) and t.is_contiguous() and t.is_cuda
+        return t if ok else torch.empty(Cout, device=x.device, dtype=torch.float32)
+    dgamma, dbeta = slot(dgamma_out), slot(dbeta_out)
+    if dw_out is not None and tuple(dw_out.shape) == tuple(w.shape) and _is_krsc_dense(dw_out):
+        dw = dw_out
+        WGRAD_STATS['in_place'] += 1
+    else:
+        WGRAD_STATS['temporary'] += 1
+        dw = krsc(torch.empty(tuple(w.shape), device=x.device, dtype=torch.float32).contiguous(memory_format=CL))
+    nbytes = L.y4_stem_bn_act_bwd_workspace(B, H, W, Cout)
+    ws = _ws(nbytes, x.device)
+    check(L.y4_stem_bn_act_bwd_f32(_ptr(x), *x.stride(), _ptr(krsc(w)), _ptr(dz), lddz, _ptr(mean), _ptr(invstd), _ptr(gamma),
+                                   _ptr(beta), ACT_IDS[act], B, H, W, Cout, _ptr(dgamma), _ptr(dbeta), _ptr(dw),
+                                   _ptr(ws), nbytes, _stream()), 'stem_bn_act_bwd')
+    return dw, dgamma, dbeta
+
+
 # ------------------------------------------------------------------ pre-split operands ("planes", csrc/conv_planes.hip)
 class Planes:
     """An NHWC activation stored as the two fp16 pieces of the f16x2 split: per pixel and 32-channel K tile
@@ -911,6 +964,22 @@ class ConvBNActFn(torch.autograd.Function):
                 ctx.dgrad_filter = dgrad_filter_buffer(x.shape[1], weight.shape[0], k, x.device)
             # conv mode 'bf16': the plane conv writes y as bf16 (half the bytes for the three BatchNorm sweeps that read it)
             ybf = ctx.y_bf16 = bool(bfm and xp is not None and weight.shape[0] % 32 == 0 and _BF16_Y)
+            # the stem (csrc/stem_fused.hip): y0 is re-formed inside the BatchNorm passes, forward and backward, and never
+            # stored -- unless the input gradient is wanted (it needs dy0 as a tensor) or the result must leave pre-split
+            cb = cfg.get('out_cat')
+            if (xp is None and residual is None and not cfg.get('out_planes') and not (cb is not None and cb.planes)
+                    and not ctx.needs_input_grad[0] and stem_fused_ok(x, weight.shape[0], k, s)):
+                if f16x2_mode():
+                    z_amax = live(cfg.get('out_amax')) if (dest is not None and _slot_ok(dest, (x.shape[0], weight.shape[0]) + tuple(x.shape[2:]))) else None
+                    if z_amax is None:
+                        z_amax = new_amax(x.device)
+                z, mean, invstd = stem_bn_act_fwd_raw(x, weight, gamma, beta, act, cfg['running_mean'], cfg['running_var'],
+                                                      cfg['nbt'], cfg['momentum'], cfg['eps'], out=dest, out_amax=z_amax)
+                ctx.save_for_backward(x, weight, mean, invstd, gamma, beta)
+                ctx.mode = 'stem_fused'
+                if io is not None:
+                    io['z_amax'] = z_amax
+                return z
             if xp is not None:
                 y, mean, invstd = conv_fwd_planes_bnstats_raw(xp, weight, k, s, cfg['running_mean'], cfg['running_var'],
                                                               cfg['nbt'], cfg['momentum'], cfg['eps'], dgrad_filter=ctx.dgrad_filter,
@@ -1014,6 +1083,30 @@ class ConvBNActFn(torch.autograd.Function):
         dy_amax = dy_pl = dyP = wq = None          # dyP / wq: pre-split dy and padded filter of a conv without BatchNorm over planes
         x_amax = live(ctx.x_amax)                     # None if the ring recycled it since forward: wgrad takes its own pass
         x_planes = getattr(ctx, 'x_planes', False)
+        if ctx.mode == 'stem_fused':
+            # one call: BatchNorm reduce + finalize, then dy0 in registers straight into the filter gradient's MFMAs
+            x, weight, mean, invstd, gamma, beta = ctx.saved_tensors
+            gp, bp, wp = cfg.get('gamma_param'), cfg.get('beta_param'), cfg.get('weight_param')
+
+            def fresh(p):
+                return p is not None and getattr(p, '_y4_grad_fresh', False) and p.grad is not None
+            sink = fresh(gp) and fresh(bp) and ctx.needs_input_grad[3] and ctx.needs_input_grad[4]
+            wsink = fresh(wp) and ctx.needs_input_grad[1]
+            dw, dgamma, dbeta = stem_bn_act_bwd_raw(x, weight, dz, mean, invstd, gamma, beta, act,
+                                                    gp.grad if sink else None, bp.grad if sink else None,
+                                                    wp.grad if wsink else None)
+            if sink and dgamma is gp.grad and dbeta is bp.grad:      # written straight into the (zeroed) DDP gradient slots
+                gp._y4_grad_fresh = bp._y4_grad_fresh = False
+                gp._y4_grad_ready()
+                bp._y4_grad_ready()
+                dgamma = dbeta = None
+            if wsink:
+                wp._y4_grad_fresh = False
+                if dw is not wp.grad:
+                    wp.grad.add_(dw)
+                wp._y4_grad_ready()
+                dw = None
+            return None, dw if ctx.needs_input_grad[1] else None, None, dgamma, dbeta, None, None
         if ctx.mode in ('bn_train', 'bn_eval_grad'):
             x, weight, y, mean, invstd, gamma, beta = ctx.saved_tensors
             gp, bp = cfg.get('gamma_param'), cfg.get('beta_param')
