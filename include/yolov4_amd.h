@@ -757,6 +757,91 @@ size_t y4_jpeg_workspace(const y4_jpeg_info* infos_host, int n);
 int y4_jpeg_decode_u8(const y4_jpeg_job* jobs_dev, const y4_jpeg_job* jobs_host, int n_jobs, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- JPEG encoding (what cv2.imwrite does for the reference's
+ * detect.py), the decoder's mirror image: everything per pixel on the device, the serial Huffman stage on the host.
+ * Baseline (SOF0), 8-bit, one interleaved scan, 1 component or YCbCr at 4:4:4 / 4:2:2 (h2v1) / 4:2:0, the standard Annex K
+ * Huffman tables, JFIF APP0; no optimised tables, restart markers, progression or EXIF.
+ *
+ * y4_jpeg_encode_setup (host): the record y4_jpeg_parse_host would give for such a file (orientation 1, no restarts) and
+ * qt_host[c] = component c's table in natural order at `quality` 1..100 (zeros for absent components): the Annex K base
+ * tables scaled by s = 5000 / quality below 50, else 200 - 2 quality; entry = clamp((base s + 50) / 100, 1, 255).
+ * Y4_ERR_SHAPE: a size outside 1..65535, ncomp not 1 or 3, sampling not 1x1 / 2x1 / 2x2 (gray: 1x1), quality outside 1..100. */
+int y4_jpeg_encode_setup(int width, int height, int ncomp, int hs, int vs, int quality, y4_jpeg_info* info_host,
+                         unsigned short* qt_host /* [3][64] */);
+
+/* Device stage: one call per BATCH, ONE launch over all jobs, images of any sizes and samplings mixed.  One record per image: */
+typedef struct y4_jpeg_enc_job {
+    const void* pixels;             /* device, uint8: HWC with 3 channels (info.ncomp 3) or HW (info.ncomp 1) */
+    short* coef;                    /* device, 16-byte aligned, info.coef_count elements */
+    long long pitch;                /* bytes per pixel row, >= 3 * width (1 * width for one component) */
+    y4_jpeg_info info;
+    int swap_rb;                    /* 0: B, G, R in memory (what y4_jpeg_decode_u8 writes); 1: R, G, B */
+    int reserved[3];
+    unsigned short qt[3][64];       /* natural order, entries 1..255, qt[1] == qt[2] */
+} y4_jpeg_enc_job;
+/* Writes the QUANTISED coefficients in exactly the layout y4_jpeg_entropy_host writes.  Dummy blocks -- grid positions of a
+ * component beyond ceil(ceil(width hs[c] / hs[0]) / 8) columns or ceil(ceil(height vs[c] / vs[0]) / 8) rows, inside the last
+ * MCU column or row (the luma of subsampled images) -- are never written.  The table is passed twice like the decoder's.
+ *
+ * The arithmetic is libjpeg-turbo's default compression path, bit for bit, all in int32:
+ *   1. Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *      Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16; one component: the byte itself;
+ *   2. pixel rows are replicated to a multiple of vs[0], pixel columns to the width of the component's real blocks; then
+ *      h2v2: (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ... along the output row; h2v1: (a + b + bias) >> 1 with bias
+ *      0, 1, 0, 1, ...; then the last DOWNSAMPLED row is replicated down to the MCU height (not the same as replicating
+ *      pixel rows further: an even height averages its last two rows);
+ *   3. subtract 128; the "islow" integer FDCT of jfdctint (CONST_BITS 13, PASS1_BITS 2, the IDCT's twelve constants): rows
+ *      first (outputs 0 and 4 shifted left by 2, the others descaled by 11), then columns (0 and 4 descaled by 2, the others
+ *      by 15);
+ *   4. d = 8 * table entry, a = |c| + (d >> 1): the result is a / d when a >= d, else 0, with the sign of c.
+ * Errors before any launch: NULL pointer (a job's pixels or coef included) Y4_ERR_NULL; n_jobs outside [1, 65535], a record
+ * that is not what y4_jpeg_encode_setup gives, a table entry outside 1..255 or differing chroma tables, a misaligned coef or
+ * table, a pitch below the row Y4_ERR_SHAPE. */
+int y4_jpeg_encode_u8(const y4_jpeg_enc_job* jobs_dev, const y4_jpeg_enc_job* jobs_host, int n_jobs, void* stream);
+
+/* Host stage (no GPU, no threads, no global state; every write checked against out_cap).  y4_jpeg_encode_host writes the file:
+ * SOI; APP0 "JFIF" 1.1, no units, density 1 x 1; one DQT per table (ids 0, 1; 8-bit; zigzag); SOF0 with components 1 / 2 / 3,
+ * luma hs * 16 + vs on table 0, chroma 0x11 on table 1; DHT DC0, AC0, DC1, AC1 (the Annex K tables); SOS; the MCU-interleaved
+ * scan (DC differences per component, ZRL, EOB, FF stuffed with 00, the last byte padded with one-bits); EOI.  One component:
+ * one DQT, two DHT.  A dummy block is coded as (DC of the block coded just before it in the same MCU, AC zero) and the
+ * buffer is never read there.  y4_jpeg_encode_bound: a size that always suffices, 1024 + 416 per block (0 for a bad record).
+ * Y4_ERR_WORKSPACE when the file does not fit out_cap (out_bytes is then 0), Y4_ERR_SHAPE for a bad record or table,
+ * Y4_ERR_FORMAT for a coefficient the standard tables cannot code (a DC difference beyond 11 bits, an AC value beyond 10;
+ * the device stage never makes one). */
+size_t y4_jpeg_encode_bound(const y4_jpeg_info* info_host);
+int y4_jpeg_encode_host(const short* coef_host, const y4_jpeg_info* info_host, const unsigned short* qt_host /* [3][64] */,
+                        void* out_host, size_t out_cap, size_t* out_bytes);
+
+/* ---------------------------------------------------------------- Box overlay (what detect.py's vis_bbox does with cv2):
+ * frames, label plates and label text drawn in place on uint8 HWC images, ONE launch per batch.  A gather: every pixel walks
+ * its image's records in order and takes the colour of the LAST record that covers it (painter's order), so overlapping
+ * boxes are deterministic, nothing races and clipping to the image is free.  The host prepares the records in integer pixels: */
+typedef struct y4_draw_box {
+    int x1, y1, x2, y2;             /* frame rectangle (inclusive corners) */
+    int half;                       /* line_width / 2: the frame is [x1-half, x2+half] x [y1-half, y2+half] without the
+                                       pixels that satisfy x1+half < x < x2-half and y1+half < y < y2-half */
+    int px1, py1, px2, py2;         /* label plate, inclusive corners, filled in the box colour; px2 < px1: none */
+    int tx, ty;                     /* top-left pixel of the first glyph cell */
+    int scale;                      /* glyph scale >= 1: a cell is 6 scale x 8 scale pixels, the glyph its top-left 5 x 7 */
+    int text_off, text_len;         /* this label's glyph indices in the job's text array */
+    unsigned char color[4];         /* B, G, R in memory order, then padding; the text is white */
+    int reserved;
+} y4_draw_box;
+typedef struct y4_draw_job {
+    void* image;                    /* device, uint8 HWC, 3 channels */
+    long long pitch;                /* bytes per row, >= 3 * width; bytes beyond 3 * width are never touched */
+    int width, height;
+    const y4_draw_box* boxes;       /* device, n_boxes records */
+    const y4_draw_box* boxes_host;  /* the same records in host memory: checked before the launch, not read by the kernel */
+    const unsigned char* text;      /* device, text_bytes glyph indices */
+    const unsigned char* glyphs;    /* device, n_glyphs x 8 bytes: rows 0..6 of a glyph, bit 4 the leftmost pixel */
+    int n_boxes, text_bytes, n_glyphs, reserved;
+} y4_draw_job;
+/* A glyph index >= n_glyphs renders as a solid cell.  Errors before the launch: NULL pointer Y4_ERR_NULL (boxes, boxes_host
+ * only when n_boxes > 0; text only when text_bytes > 0; glyphs only when n_glyphs > 0); n_images outside [1, 65535], a size
+ * below 1, a pitch below 3 * width, a negative count, half < 0, scale < 1 or a text range outside [0, text_bytes] Y4_ERR_SHAPE. */
+int y4_draw_boxes_u8(const y4_draw_job* jobs_dev, const y4_draw_job* jobs_host, int n_images, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

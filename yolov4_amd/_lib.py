@@ -128,6 +128,11 @@ PROTOTYPES = {
     'y4_jpeg_entropy_host': (I, [P, Z, P, P, L, P]),
     'y4_jpeg_workspace': (Z, [P, I]),
     'y4_jpeg_decode_u8': (I, [P, P, I, P, Z, P]),
+    'y4_jpeg_encode_setup': (I, [I, I, I, I, I, I, P, P]),
+    'y4_jpeg_encode_u8': (I, [P, P, I, P]),
+    'y4_jpeg_encode_bound': (Z, [P]),
+    'y4_jpeg_encode_host': (I, [P, P, P, P, Z, P]),
+    'y4_draw_boxes_u8': (I, [P, P, I, P]),
 }
 
 ERR_FORMAT, ERR_UNSUPPORTED = 6, 7
@@ -157,6 +162,26 @@ class JpegJob(ctypes.Structure):
     """y4_jpeg_job (512 bytes)"""
     _fields_ = [('coef', c_void_p), ('out', c_void_p), ('out_pitch', c_longlong), ('ws_offset', c_longlong),
                 ('info', JpegInfo), ('apply_orientation', c_int), ('swap_rb', c_int), ('qt', (ctypes.c_uint16 * 64) * 3)]
+
+
+class JpegEncJob(ctypes.Structure):
+    """y4_jpeg_enc_job (512 bytes)"""
+    _fields_ = [('pixels', c_void_p), ('coef', c_void_p), ('pitch', c_longlong), ('info', JpegInfo), ('swap_rb', c_int),
+                ('reserved', c_int * 3), ('qt', (ctypes.c_uint16 * 64) * 3)]
+
+
+class DrawBox(ctypes.Structure):
+    """y4_draw_box (64 bytes)"""
+    _fields_ = [('x1', c_int), ('y1', c_int), ('x2', c_int), ('y2', c_int), ('half', c_int), ('px1', c_int), ('py1', c_int),
+                ('px2', c_int), ('py2', c_int), ('tx', c_int), ('ty', c_int), ('scale', c_int), ('text_off', c_int),
+                ('text_len', c_int), ('color', ctypes.c_uint8 * 4), ('reserved', c_int)]
+
+
+class DrawJob(ctypes.Structure):
+    """y4_draw_job (72 bytes)"""
+    _fields_ = [('image', c_void_p), ('pitch', c_longlong), ('width', c_int), ('height', c_int), ('boxes', c_void_p),
+                ('boxes_host', c_void_p), ('text', c_void_p), ('glyphs', c_void_p), ('n_boxes', c_int), ('text_bytes', c_int),
+                ('n_glyphs', c_int), ('reserved', c_int)]
 
 
 _lib = None

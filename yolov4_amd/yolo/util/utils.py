@@ -118,6 +118,15 @@ def yolobox2xywh(box, info_img):
     return [x1 / dst_w * src_w, y1 / dst_h * src_h, box_w, box_h]
 
 
+def yolobox2yxyx(box, info_img):
+    """(y1, x1, y2, x2) in network-input pixels -> [y1, x1, y2, x2] in source-image pixels
+    (yolo/util/utils.py:312-341); `info_img` = (src_h, src_w, dst_h, dst_w).  Python floats or float64 arrays: the
+    reference's double arithmetic in its order (multiply, then divide)."""
+    src_h, src_w, dst_h, dst_w = info_img
+    y1, x1, y2, x2 = box
+    return [y1 * src_h / dst_h, x1 * src_w / dst_w, y2 * src_h / dst_h, x2 * src_w / dst_w]
+
+
 def detections_to_coco(detections, img_info, image_id, class_ids=COCO_CLASS_IDS):
     """One image's postprocess() result [n,7] (or None) -> list of COCO result dicts, as validate() builds
     them (yolo/engine/build.py:144-164).  The reference converts every fp32 number to a Python float and
