@@ -465,6 +465,61 @@ int y4_post_nms_f32(const float* prediction, int B, long long N, int n_classes, 
                     float nms_thre, const int* seg_offsets /* [B*C+1] device */, long long total_candidates,
                     float* det_rows /* [total,7] */, int* kept /* [B*C] */,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* ---------------------------------------------------------------- post-processing with options
+ * The same stages with a selectable overlap measure, Soft-NMS, class-agnostic segments and a per-image cap.  With
+ * {Y4_NMS_IOU, Y4_SOFT_NONE, agnostic 0, max_det 0} the _ex entries launch the kernels of the entries above.
+ *
+ * Candidates: box i, class c with s0 = obj_i * cls_ic (one fp32 product) >= conf_thre.  A segment is (image, class); with
+ * agnostic = 1 it is the whole image.  Sort key: score descending, then index ascending; the index is the box i, for
+ * agnostic segments i * C + c (lower box, then lower class), which needs N * C < 2^31 (else Y4_ERR_SHAPE).
+ * Measure of candidate a against selected box o (areas (x2 - x1) * (y2 - y1); each step one fp32 operation, in this order):
+ *   tl = max(a.xy1, o.xy1), br = min(a.xy2, o.xy2), en = tl < br on both axes ? 1 : 0,
+ *   inter = ((br.x - tl.x) * (br.y - tl.y)) * en, iou = inter / ((area_a + area_o) - inter)                    [Y4_NMS_IOU]
+ *   dx = ((a.x1 + a.x2) - (o.x1 + o.x2)) * 0.5, dy likewise, rho2 = dx * dx + dy * dy,
+ *   ew = max(a.x2, o.x2) - min(a.x1, o.x1), eh likewise, c2 = ew * ew + eh * eh,
+ *   diou = iou - (c2 == 0 ? 0 : rho2 / c2)                                                                      [Y4_NMS_DIOU]
+ * Hard mode (Y4_SOFT_NONE): greedy in key order; a candidate is dropped when its measure against a kept box is
+ *   >= nms_thre (a NaN measure keeps it); a segment stops after max_det survivors when max_det > 0.
+ * Soft mode: W_j = 1, current score s0_j * W_j.  Repeat: select the remaining j with the largest current score (ties: key
+ *   order); stop when none remains or the segment has emitted max_det rows (max_det > 0); emit it; for every remaining j
+ *   ov = measure(j, selected) > 0 ? measure : 0;  Y4_SOFT_LINEAR: w = ov >= nms_thre ? 1 - ov : 1;
+ *   Y4_SOFT_GAUSSIAN: w = expf(-(ov * ov) / sigma);  W_j = W_j * w;  j is removed when s0_j * W_j < conf_thre.
+ *   Emitted rows are (x1, y1, x2, y2, obj, cls_conf * W, cls): row[4] * row[5] is the decayed score.
+ * Not supported: the beta exponent of Darknet's DIoU-NMS (powf would give up the bit-exact restatement).
+ *
+ * y4_post_count_ex_f32: as y4_post_count_f32; agnostic = 1 counts per image into counts[B].
+ * y4_post_nms_ex_f32: as y4_post_nms_f32 on B * C (agnostic: B) segments; one 256-thread block per segment, Soft-NMS state
+ *   in LDS up to 2048 candidates and in the workspace above.  kept[] has one entry per segment.
+ * y4_post_topk_compact_f32: y4_post_compact_f32 behind a per-image cap: of the kept rows of an image's segs_per_image
+ *   segments the max_det (>= 1) with the highest row[4] * row[5] (fp32) stay (ties: lower class, then earlier place in the
+ *   segment), in the usual output order.  total_candidates = the capacity the segment offsets were clamped to.
+ * Errors before any launch: NULL pointer Y4_ERR_NULL; an unknown metric / soft kind, sigma <= 0 with Y4_SOFT_GAUSSIAN,
+ * agnostic outside {0, 1}, max_det < 0 (top-k: < 1) or a bad shape Y4_ERR_SHAPE (workspace query: 0); workspace too small
+ * Y4_ERR_WORKSPACE. */
+#define Y4_NMS_IOU 0
+#define Y4_NMS_DIOU 1
+#define Y4_SOFT_NONE 0
+#define Y4_SOFT_LINEAR 1
+#define Y4_SOFT_GAUSSIAN 2
+typedef struct y4_nms_opts {
+    int metric;      /* Y4_NMS_*  */
+    int soft;        /* Y4_SOFT_* */
+    float sigma;     /* Gaussian decay; > 0 */
+    int agnostic;    /* 0 | 1 */
+    int max_det;     /* 0 = no cap */
+    int reserved[3]; /* 0 */
+} y4_nms_opts;       /* 32 bytes */
+int y4_post_count_ex_f32(float* prediction, int B, long long N, int n_classes, float conf_thre,
+                         int convert_xyxy, int agnostic, int* counts, void* stream);
+size_t y4_post_nms_ex_workspace(long long total_candidates, int n_segments, const y4_nms_opts* opts);
+int y4_post_nms_ex_f32(const float* prediction, int B, long long N, int n_classes, float conf_thre, float nms_thre,
+                       const y4_nms_opts* opts /* host */, const int* seg_offsets /* [segments+1] device */,
+                       long long total_candidates, float* det_rows /* [total,7] */, int* kept /* [segments] */,
+                       void* workspace, size_t workspace_bytes, void* stream);
+size_t y4_post_topk_workspace(long long total_candidates, int n_segments);
+int y4_post_topk_compact_f32(const float* det_rows, const int* seg_offsets, const int* kept, int B, int segs_per_image,
+                             int max_det, long long total_candidates, float* out_rows, int* out_offsets,
+                             int* img_offsets, void* workspace, size_t workspace_bytes, void* stream);
 /* plain greedy NMS on one list (nms(), utils.py:32): boxes [R,4] xyxy, order given by
  * score desc / index asc; writes keep flags in sorted order and the sorted index list. */
 size_t y4_nms_workspace(long long R);

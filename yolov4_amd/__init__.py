@@ -10,7 +10,7 @@ Drop-in for the hot-path modules of zjykzj/YOLOv4:
     yolo.model.yololayer.YOLOLayer                yolov4_amd.yolo.model.yololayer
     yolo.model.yololoss.YOLOLoss                  yolov4_amd.yolo.model.yololoss
     yolo.model.build.build_model/build_criterion  yolov4_amd.yolo.model.build
-    yolo.util.utils.postprocess / nms             yolov4_amd.yolo.util.utils
+    yolo.util.utils.postprocess / nms             yolov4_amd.yolo.util.utils (+ postprocess_nms: DIoU- / Soft- / agnostic NMS)
 
 All arithmetic runs in libyolov4_amd.so (hand-written HIP, C ABI in
 include/yolov4_amd.h); there is no CPU or PyTorch-op fallback.

@@ -95,6 +95,11 @@ PROTOTYPES = {
     'y4_post_compact_f32': (I, [P, P, P, I, I, P, P, P, P]),
     'y4_post_nms_workspace': (Z, [L, I]),
     'y4_post_nms_f32': (I, [P, I, L, I, F, F, P, L, P, P, P, Z, P]),
+    'y4_post_count_ex_f32': (I, [P, I, L, I, F, I, I, P, P]),
+    'y4_post_nms_ex_workspace': (Z, [L, I, P]),
+    'y4_post_nms_ex_f32': (I, [P, I, L, I, F, F, P, P, L, P, P, P, Z, P]),
+    'y4_post_topk_workspace': (Z, [L, I]),
+    'y4_post_topk_compact_f32': (I, [P, P, P, I, I, I, L, P, P, P, P, Z, P]),
     'y4_nms_workspace': (Z, [L]),
     'y4_nms_f32': (I, [P, P, L, F, I, P, P, P, Z, P]),
     'y4_bboxes_iou_f32': (I, [P, L, P, L, I, P, P]),
@@ -136,6 +141,16 @@ PROTOTYPES = {
 }
 
 ERR_FORMAT, ERR_UNSUPPORTED = 6, 7
+
+
+NMS_METRICS = {'iou': 0, 'diou': 1}
+NMS_SOFT = {None: 0, 'linear': 1, 'gaussian': 2}
+
+
+class NmsOpts(ctypes.Structure):
+    """y4_nms_opts (32 bytes)"""
+    _fields_ = [('metric', c_int), ('soft', c_int), ('sigma', c_float), ('agnostic', c_int), ('max_det', c_int),
+                ('reserved', c_int * 3)]
 
 
 class AugSrc(ctypes.Structure):

@@ -5,6 +5,11 @@
 // This file is compiled with -ffp-contract=off: IoU comparisons against thresholds must follow
 // the reference's separate fp32 multiply / add / divide sequence bit for bit
 // (yolo/model/yololoss.py:56-91, yolo/util/utils.py:64-77).
+//
+// Post-processing options (include/yolov4_amd.h): the overlap measure (IoU | DIoU) is a template
+// parameter of the suppression kernels, segments are (image, class) or whole images (AGN), Soft-NMS (linear | Gaussian
+// decay) is one block per segment with its state in LDS, a per-image cap sorts the kept rows of an image.  The measure's
+// fp32 operation order is written out at nms_measure; a float32 restatement of it is bit-equal (no fma contraction here).
 #include <stdlib.h>
 #include "common.h"
 
@@ -762,6 +767,8 @@ __device__ __forceinline__ void post_load_tile(const float* __restrict__ pred, l
     }
 }
 
+// AGN (class-agnostic segments): one segment per image, counts[b]; else counts[b * C + c]
+template <bool AGN>
 __global__ __launch_bounds__(256) void post_count_tiled_kernel(float* __restrict__ pred, int B, long long N, int C,
                                                                float conf, int convert, int* __restrict__ counts) {
     extern __shared__ float post_smem[];
@@ -793,7 +800,7 @@ __global__ __launch_bounds__(256) void post_count_tiled_kernel(float* __restrict
                     const long long i = row0 + r;
                     if (i < b0_end) atomicAdd(&hist[c], 1);
                     else if (i < b0_end + N) atomicAdd(&hist[C + c], 1);
-                    else atomicAdd(&counts[(int)(i / N) * C + c], 1);
+                    else atomicAdd(&counts[AGN ? (int)(i / N) : (int)(i / N) * C + c], 1);
                 }
             }
         }
@@ -801,7 +808,7 @@ __global__ __launch_bounds__(256) void post_count_tiled_kernel(float* __restrict
         for (int i = threadIdx.x; i < 2 * C; i += 256) {
             const int v = hist[i];
             const int b = b0 + (i >= C ? 1 : 0);
-            if (v && b < B) atomicAdd(&counts[b * C + (i >= C ? i - C : i)], v);
+            if (v && b < B) atomicAdd(&counts[AGN ? b : b * C + (i >= C ? i - C : i)], v);
         }
         __syncthreads();
     }
@@ -809,6 +816,8 @@ __global__ __launch_bounds__(256) void post_count_tiled_kernel(float* __restrict
 
 __device__ __forceinline__ unsigned long long make_key(float score, unsigned idx);
 
+// AGN: the key's low word is box * C + c (ties: lower box, then lower class); else the box index
+template <bool AGN>
 __global__ __launch_bounds__(256) void post_fill_tiled_kernel(const float* __restrict__ pred, int B, long long N, int C,
                                                               float conf, const int* __restrict__ seg_off,
                                                               int* __restrict__ cursor,
@@ -831,11 +840,12 @@ __global__ __launch_bounds__(256) void post_fill_tiled_kernel(const float* __res
                 if (cc * obj >= conf) {
                     const long long i = row0 + r;
                     const int b = (int)(i / N);
-                    const int seg = b * C + c;
+                    const int seg = AGN ? b : b * C + c;
                     const int slot = atomicAdd(&cursor[seg], 1);
+                    const unsigned box = (unsigned)(i - (long long)b * N);
                     // (a segment truncated by a too-small candidate buffer takes what fits; the host re-runs with room)
                     if (slot < seg_off[seg + 1] - seg_off[seg])
-                        keys[seg_off[seg] + slot] = make_key(obj * cc, (unsigned)(i - (long long)b * N));   // utils.py:209
+                        keys[seg_off[seg] + slot] = make_key(obj * cc, AGN ? box * (unsigned)C + (unsigned)c : box);   // utils.py:209
                 }
             }
         }
@@ -843,6 +853,7 @@ __global__ __launch_bounds__(256) void post_fill_tiled_kernel(const float* __res
     }
 }
 
+template <bool AGN>
 __global__ __launch_bounds__(256) void post_count_kernel(float* __restrict__ pred, int B, long long N, int C,
                                                          float conf, int convert, int* __restrict__ counts) {
     const long long total = (long long)B * N;
@@ -857,7 +868,7 @@ __global__ __launch_bounds__(256) void post_count_kernel(float* __restrict__ pre
         const int b = (int)(i / N);
         const float obj = p[4];
         for (int c = 0; c < C; ++c)
-            if (p[5 + c] * obj >= conf) atomicAdd(&counts[b * C + c], 1);
+            if (p[5 + c] * obj >= conf) atomicAdd(&counts[AGN ? b : b * C + c], 1);
     }
 }
 
@@ -868,6 +879,7 @@ __device__ __forceinline__ unsigned long long make_key(float score, unsigned idx
     return ((unsigned long long)(~u) << 32) | idx;
 }
 
+template <bool AGN>
 __global__ __launch_bounds__(256) void post_fill_kernel(const float* __restrict__ pred, int B, long long N, int C,
                                                         float conf, const int* __restrict__ seg_off,
                                                         int* __restrict__ cursor, unsigned long long* __restrict__ keys) {
@@ -882,10 +894,10 @@ __global__ __launch_bounds__(256) void post_fill_kernel(const float* __restrict_
         for (int c = 0; c < C; ++c) {
             const float cc = p[5 + c];
             if (cc * obj >= conf) {
-                const int seg = b * C + c;
+                const int seg = AGN ? b : b * C + c;
                 const int slot = atomicAdd(&cursor[seg], 1);
                 if (slot < seg_off[seg + 1] - seg_off[seg])
-                    keys[seg_off[seg] + slot] = make_key(obj * cc, box);  // utils.py:209 score = obj*cls_conf
+                    keys[seg_off[seg] + slot] = make_key(obj * cc, AGN ? box * (unsigned)C + (unsigned)c : box);  // utils.py:209 score = obj*cls_conf
             }
         }
     }
@@ -934,7 +946,27 @@ struct NmsShared {
     int nk;
 };
 
-template <typename BoxFn>
+// The overlap of candidate a against the already selected box o, areas (x2 - x1) * (y2 - y1) computed by the caller.
+// Y4_NMS_IOU: utils.py:64-77.  Y4_NMS_DIOU: iou - rho2 / c2 with, each step one fp32 operation in this order,
+//   dx = ((a.x1 + a.x2) - (o.x1 + o.x2)) * 0.5, dy likewise, rho2 = dx * dx + dy * dy,
+//   ew = max(a.x2, o.x2) - min(a.x1, o.x1), eh likewise, c2 = ew * ew + eh * eh, penalty = c2 == 0 ? 0 : rho2 / c2.
+template <int MEASURE>
+__device__ __forceinline__ float nms_measure(const float4 a, float area_a, const float4 o, float area_o) {
+    const float tlx = fmaxf(a.x, o.x), tly = fmaxf(a.y, o.y);
+    const float brx = fminf(a.z, o.z), bry = fminf(a.w, o.w);
+    const float en = (tlx < brx && tly < bry) ? 1.f : 0.f;
+    const float inter = ((brx - tlx) * (bry - tly)) * en;
+    const float iou = inter / ((area_a + area_o) - inter);
+    if (MEASURE == Y4_NMS_IOU) return iou;
+    const float dx = ((a.x + a.z) - (o.x + o.z)) * 0.5f, dy = ((a.y + a.w) - (o.y + o.w)) * 0.5f;
+    const float rho2 = dx * dx + dy * dy;
+    const float ew = fmaxf(a.z, o.z) - fminf(a.x, o.x), eh = fmaxf(a.w, o.w) - fminf(a.y, o.y);
+    const float c2 = ew * ew + eh * eh;
+    const float pen = c2 == 0.f ? 0.f : rho2 / c2;
+    return iou - pen;
+}
+
+template <int MEASURE, typename BoxFn>
 __device__ int block_greedy_nms(int n, float thresh, int limit, BoxFn box_of, float4* kept_box, float* kept_area,
                                 int* kept_sorted_pos, NmsShared& sh) {
     int kept = 0;                                               // uniform
@@ -953,13 +985,7 @@ __device__ int block_greedy_nms(int n, float thresh, int limit, BoxFn box_of, fl
             const int kn = min(256, kept - k0);
             if (alive)
                 for (int k = 0; k < kn; ++k) {
-                    const float4 o = sh.kb[k];
-                    const float tlx = fmaxf(bx.x, o.x), tly = fmaxf(bx.y, o.y);
-                    const float brx = fminf(bx.z, o.z), bry = fminf(bx.w, o.w);
-                    const float en = (tlx < brx && tly < bry) ? 1.f : 0.f;
-                    const float inter = ((brx - tlx) * (bry - tly)) * en;
-                    const float iou = inter / ((area + sh.ka[k]) - inter);
-                    if (iou >= thresh) { alive = false; break; }
+                    if (nms_measure<MEASURE>(bx, area, sh.kb[k], sh.ka[k]) >= thresh) { alive = false; break; }
                 }
         }
         // (B) intra-chunk
@@ -975,14 +1001,8 @@ __device__ int block_greedy_nms(int n, float thresh, int limit, BoxFn box_of, fl
         unsigned long long mk[4] = {0, 0, 0, 0};
         if (alive)
             for (int u = threadIdx.x + 1; u < 256 && s + u < n; ++u) {
-                const float4 o = sh.kb[u];
                 // candidate u is tested against already-selected t: area_u + area_t (utils.py:76)
-                const float tlx = fmaxf(o.x, bx.x), tly = fmaxf(o.y, bx.y);
-                const float brx = fminf(o.z, bx.z), bry = fminf(o.w, bx.w);
-                const float en = (tlx < brx && tly < bry) ? 1.f : 0.f;
-                const float inter = ((brx - tlx) * (bry - tly)) * en;
-                const float iou = inter / ((sh.ka[u] + area) - inter);
-                if (iou >= thresh) mk[u >> 6] |= 1ull << (u & 63);
+                if (nms_measure<MEASURE>(sh.kb[u], sh.ka[u], bx, area) >= thresh) mk[u >> 6] |= 1ull << (u & 63);
             }
 #pragma unroll
         for (int q = 0; q < 4; ++q) sh.mask[threadIdx.x][q] = mk[q];
@@ -1017,8 +1037,10 @@ __device__ int block_greedy_nms(int n, float thresh, int limit, BoxFn box_of, fl
 
 constexpr int NMS_LDS_KEYS = 2048;
 
+// AGN: segment = image, key low word = box * C + c; `limit` > 0 stops a segment at that many survivors
+template <int MEASURE, bool AGN>
 __global__ __launch_bounds__(256) void post_nms_kernel(const float* __restrict__ pred, long long N, int C,
-                                                       float thresh, const int* __restrict__ seg_off,
+                                                       float thresh, int limit, const int* __restrict__ seg_off,
                                                        unsigned long long* __restrict__ keys,
                                                        float4* __restrict__ kbox, float* __restrict__ karea,
                                                        int* __restrict__ kpos, float* __restrict__ det_rows,
@@ -1028,7 +1050,7 @@ __global__ __launch_bounds__(256) void post_nms_kernel(const float* __restrict__
     const int off = seg_off[seg];
     const int n = seg_off[seg + 1] - off;
     if (n == 0) { if (threadIdx.x == 0) kept_out[seg] = 0; return; }
-    const int b = seg / C, c = seg - b * C;
+    const int b = AGN ? seg : seg / C, c = AGN ? 0 : seg - b * C;
     const int n_ch = 5 + C;
     unsigned long long* k = keys + off;
     if (n <= NMS_LDS_KEYS) {
@@ -1044,16 +1066,148 @@ __global__ __launch_bounds__(256) void post_nms_kernel(const float* __restrict__
     }
     const float* img = pred + (long long)b * N * n_ch;
     auto box_of = [&](int i) {
-        const unsigned idx = (unsigned)(k[i] & 0xffffffffull);
+        const unsigned low = (unsigned)(k[i] & 0xffffffffull);
+        const unsigned idx = AGN ? low / (unsigned)C : low;
         const float* p = img + (long long)idx * n_ch;
         return make_float4(p[0], p[1], p[2], p[3]);
     };
-    const int kept = block_greedy_nms(n, thresh, 0, box_of, kbox + off, karea + off, kpos + off, sh);
+    const int kept = block_greedy_nms<MEASURE>(n, thresh, limit, box_of, kbox + off, karea + off, kpos + off, sh);
     for (int r = threadIdx.x; r < kept; r += blockDim.x) {
-        const unsigned idx = (unsigned)(k[kpos[off + r]] & 0xffffffffull);
+        const unsigned low = (unsigned)(k[kpos[off + r]] & 0xffffffffull);
+        const unsigned idx = AGN ? low / (unsigned)C : low;
+        const int cls = AGN ? (int)(low - idx * (unsigned)C) : c;
         const float* p = img + (long long)idx * n_ch;
         float* o = det_rows + (long long)(off + r) * 7;
-        o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; o[4] = p[4]; o[5] = p[5 + c]; o[6] = (float)c;
+        o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; o[4] = p[4]; o[5] = p[5 + cls]; o[6] = (float)cls;
+    }
+    if (threadIdx.x == 0) kept_out[seg] = kept;
+}
+
+// ---- Soft-NMS (Bodla et al.), one block per segment.  Candidate j = sorted position j (score descending, key index
+// ascending) carries a weight W_j (1 at the start) and the current score s0_j * W_j.  A round emits the alive candidate with
+// the largest current score (ties: lower sorted position) and decays every other alive j by
+//   ov = measure(j, selected) > 0 ? measure : 0;   linear: w = ov >= thresh ? 1 - ov : 1;   gaussian: w = expf(-(ov * ov) / sigma)
+//   W_j = W_j * w;   j leaves when s0_j * W_j < conf.
+// The decay sweep of one round is also the arg-max of the next: a thread keeps the best (score, position) of what it
+// swept, 64 lanes fold by shuffles, the four waves through LDS (two buffers in turn: one barrier per round).  Every loop is
+// bounded by n or by `rounds` = min(n, limit or n), both read before it starts.
+struct SoftRed { float v[2][4]; int j[2][4]; };
+
+__device__ __forceinline__ float key_score(unsigned long long key) {
+    const unsigned u = ~(unsigned)(key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+template <int MEASURE>
+__device__ __forceinline__ int soft_nms_rounds(int n, int rounds, int soft, float thresh, float sigma, float conf,
+                                               const float4* sb, const float* ss0, float* sW, unsigned char* sal,
+                                               int* epos, float* ew, SoftRed& red) {
+    int sel = 0, e = 0;                                         // uniform; position 0 holds the largest s0 and every W is 1
+    for (int r = 0; r < rounds; ++r) {
+        const float4 bs = sb[sel];
+        const float as = (bs.z - bs.x) * (bs.w - bs.y);
+        if (threadIdx.x == 0) { epos[e] = sel; ew[e] = sW[sel]; sal[sel] = 0; }
+        ++e;
+        if (r + 1 == rounds) break;
+        float bv = 0.f;
+        int bj = -1;
+        for (int j = threadIdx.x; j < n; j += 256) {
+            if (j == sel || !sal[j]) continue;
+            const float4 bx = sb[j];
+            const float m = nms_measure<MEASURE>(bx, (bx.z - bx.x) * (bx.w - bx.y), bs, as);
+            const float ov = m > 0.f ? m : 0.f;
+            const float w = soft == Y4_SOFT_LINEAR ? (ov >= thresh ? 1.f - ov : 1.f) : expf(-(ov * ov) / sigma);
+            const float W = sW[j] * w;
+            sW[j] = W;
+            const float cur = ss0[j] * W;
+            if (cur < conf) sal[j] = 0;
+            else if (bj < 0 || cur > bv) { bv = cur; bj = j; }  // ascending j: the first of equal scores stays
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_down(bv, off, 64);
+            const int oj = __shfl_down(bj, off, 64);
+            if (oj >= 0 && (bj < 0 || ov > bv || (ov == bv && oj < bj))) { bv = ov; bj = oj; }
+        }
+        const int buf = r & 1;
+        if ((threadIdx.x & 63) == 0) { red.v[buf][threadIdx.x >> 6] = bv; red.j[buf][threadIdx.x >> 6] = bj; }
+        __syncthreads();
+        bv = red.v[buf][0]; bj = red.j[buf][0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) {
+            const float ov = red.v[buf][q];
+            const int oj = red.j[buf][q];
+            if (oj >= 0 && (bj < 0 || ov > bv || (ov == bv && oj < bj))) { bv = ov; bj = oj; }
+        }
+        if (bj < 0) break;                                      // nothing remains
+        sel = bj;
+    }
+    return e;
+}
+
+template <int MEASURE, bool AGN>
+__global__ __launch_bounds__(256) void post_soft_nms_kernel(const float* __restrict__ pred, long long N, int C, float thresh,
+                                                            int soft, float sigma, float conf, int limit,
+                                                            const int* __restrict__ seg_off,
+                                                            unsigned long long* __restrict__ keys,
+                                                            float4* __restrict__ gbox, float* __restrict__ gs0,
+                                                            float* __restrict__ gW, unsigned char* __restrict__ galive,
+                                                            int* __restrict__ epos, float* __restrict__ ew,
+                                                            float* __restrict__ det_rows, int* __restrict__ kept_out) {
+    // boxes 32 KiB | s0 8 KiB | W 8 KiB | alive 2 KiB; the sort's key copy (16 KiB) uses the box area before the boxes do
+    __shared__ __attribute__((aligned(16))) unsigned char lds[NMS_LDS_KEYS * 25];
+    __shared__ SoftRed red;
+    const int seg = blockIdx.x;
+    const int off = seg_off[seg];
+    const int n = seg_off[seg + 1] - off;
+    if (n == 0) { if (threadIdx.x == 0) kept_out[seg] = 0; return; }
+    const int b = AGN ? seg : seg / C, c = AGN ? 0 : seg - b * C;
+    const int n_ch = 5 + C;
+    unsigned long long* k = keys + off;
+    const bool in_lds = n <= NMS_LDS_KEYS;
+    if (in_lds) {
+        unsigned long long* skeys = reinterpret_cast<unsigned long long*>(lds);
+        for (int i = threadIdx.x; i < n; i += 256) skeys[i] = k[i];
+        __syncthreads();
+        block_bitonic_sort(skeys, n);
+        for (int i = threadIdx.x; i < n; i += 256) k[i] = skeys[i];
+        __syncthreads();
+    } else {
+        block_bitonic_sort(k, n);
+    }
+    const float* img = pred + (long long)b * N * n_ch;
+    float4* sb = in_lds ? reinterpret_cast<float4*>(lds) : gbox + off;
+    float* ss0 = in_lds ? reinterpret_cast<float*>(lds + NMS_LDS_KEYS * 16) : gs0 + off;
+    float* sW = in_lds ? reinterpret_cast<float*>(lds + NMS_LDS_KEYS * 20) : gW + off;
+    unsigned char* sal = in_lds ? lds + NMS_LDS_KEYS * 24 : galive + off;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const unsigned long long key = k[i];
+        const unsigned low = (unsigned)(key & 0xffffffffull);
+        const unsigned idx = AGN ? low / (unsigned)C : low;
+        const float* p = img + (long long)idx * n_ch;
+        sb[i] = make_float4(p[0], p[1], p[2], p[3]);
+        ss0[i] = key_score(key);
+        sW[i] = 1.f;
+        sal[i] = 1;
+    }
+    __syncthreads();
+    const int rounds = (limit > 0 && limit < n) ? limit : n;
+    int kept;
+    if (in_lds)
+        kept = soft_nms_rounds<MEASURE>(n, rounds, soft, thresh, sigma, conf, reinterpret_cast<const float4*>(lds),
+                                        reinterpret_cast<const float*>(lds + NMS_LDS_KEYS * 16),
+                                        reinterpret_cast<float*>(lds + NMS_LDS_KEYS * 20), lds + NMS_LDS_KEYS * 24,
+                                        epos + off, ew + off, red);
+    else
+        kept = soft_nms_rounds<MEASURE>(n, rounds, soft, thresh, sigma, conf, gbox + off, gs0 + off, gW + off, galive + off,
+                                        epos + off, ew + off, red);
+    __syncthreads();
+    for (int r = threadIdx.x; r < kept; r += 256) {
+        const unsigned low = (unsigned)(k[epos[off + r]] & 0xffffffffull);
+        const unsigned idx = AGN ? low / (unsigned)C : low;
+        const int cls = AGN ? (int)(low - idx * (unsigned)C) : c;
+        const float* p = img + (long long)idx * n_ch;
+        float* o = det_rows + (long long)(off + r) * 7;
+        o[0] = p[0]; o[1] = p[1]; o[2] = p[2]; o[3] = p[3]; o[4] = p[4]; o[5] = p[5 + cls] * ew[off + r]; o[6] = (float)cls;
     }
     if (threadIdx.x == 0) kept_out[seg] = kept;
 }
@@ -1074,7 +1228,7 @@ __global__ __launch_bounds__(256) void nms_single_kernel(const float* __restrict
         const unsigned idx = (unsigned)(keys[i] & 0xffffffffull);
         return make_float4(boxes[idx * 4], boxes[idx * 4 + 1], boxes[idx * 4 + 2], boxes[idx * 4 + 3]);
     };
-    const int kept = block_greedy_nms(R, thresh, limit, box_of, kbox, karea, kpos, sh);
+    const int kept = block_greedy_nms<Y4_NMS_IOU>(R, thresh, limit, box_of, kbox, karea, kpos, sh);
     for (int r = threadIdx.x; r < kept; r += blockDim.x) keep_idx[r] = (int)(keys[kpos[r]] & 0xffffffffull);
     if (threadIdx.x == 0) *n_keep = kept;
 }
@@ -1138,7 +1292,82 @@ __global__ __launch_bounds__(64) void post_compact_kernel(const float* __restric
     for (int i = threadIdx.x; i < n; i += 64) dst[i] = src[i];
 }
 
+// ---- per-image cap: one block per image gives each kept row of its S segments the key (row[4] * row[5] descending, row
+// position in det_rows ascending = class, then place in the segment), sorts them and flags the first max_det;
+// kept2[s] = flagged rows of segment s.
+__global__ __launch_bounds__(256) void post_topk_kernel(const float* __restrict__ det_rows, const int* __restrict__ seg_off,
+                                                        const int* __restrict__ kept, int S, int max_det,
+                                                        unsigned long long* __restrict__ tkeys, int* __restrict__ flags,
+                                                        int* __restrict__ kept2) {
+    __shared__ unsigned long long skeys[NMS_LDS_KEYS];
+    __shared__ int cnt;
+    const int s0 = blockIdx.x * S;
+    const int base = seg_off[s0];
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    for (int s = s0; s < s0 + S; ++s) {
+        const int off = seg_off[s], ks = kept[s];
+        for (int r = threadIdx.x; r < ks; r += 256) {
+            const int pos = off + r;
+            const float* row = det_rows + (long long)pos * 7;
+            const int slot = atomicAdd(&cnt, 1);               // any order: the sort below fixes it (keys are distinct)
+            tkeys[base + slot] = make_key(row[4] * row[5], (unsigned)pos);
+            flags[pos] = 0;
+        }
+    }
+    __syncthreads();
+    const int nk = cnt;                                        // <= the image's candidates: inside its span of tkeys
+    unsigned long long* k = tkeys + base;
+    if (nk > max_det) {
+        if (nk <= NMS_LDS_KEYS) {
+            for (int i = threadIdx.x; i < nk; i += 256) skeys[i] = k[i];
+            __syncthreads();
+            block_bitonic_sort(skeys, nk);
+            for (int i = threadIdx.x; i < max_det; i += 256) k[i] = skeys[i];
+            __syncthreads();
+        } else {
+            block_bitonic_sort(k, nk);
+        }
+    }
+    const int nflag = nk < max_det ? nk : max_det;
+    for (int i = threadIdx.x; i < nflag; i += 256) flags[(unsigned)(k[i] & 0xffffffffull)] = 1;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    for (int s = s0 + (threadIdx.x >> 6); s < s0 + S; s += 4) {
+        const int off = seg_off[s], ks = kept[s];
+        int v = 0;
+        for (int r = lane; r < ks; r += 64) v += flags[off + r];
+        for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
+        if (lane == 0) kept2[s] = v;
+    }
+}
+// the flagged rows of segment s, in their order -> out_rows[out_off[s] ..)
+__global__ __launch_bounds__(64) void post_compact_flagged_kernel(const float* __restrict__ det_rows,
+                                                                  const int* __restrict__ seg_off,
+                                                                  const int* __restrict__ kept, const int* __restrict__ flags,
+                                                                  const int* __restrict__ out_off,
+                                                                  float* __restrict__ out_rows) {
+    const int s = blockIdx.x;
+    const int n = kept[s], off = seg_off[s];
+    int run = out_off[s];
+    for (int r0 = 0; r0 < n; r0 += 64) {
+        const int r = r0 + threadIdx.x;
+        const bool f = r < n && flags[off + r] != 0;
+        const unsigned long long m = __ballot(f);
+        if (f) {
+            const float* src = det_rows + (long long)(off + r) * 7;
+            float* dst = out_rows + (long long)(run + __popcll(m & ((1ull << threadIdx.x) - 1ull))) * 7;
+#pragma unroll
+            for (int q = 0; q < 7; ++q) dst[q] = src[q];
+        }
+        run += __popcll(m);
+    }
+}
+
 struct PostWs { size_t keys, cursor, kbox, karea, kpos, total; };
+// the Soft-NMS state of segments above the LDS bound, and the emitted (position, weight) lists, behind the hard layout
+struct PostExWs { PostWs base; size_t w, ew, alive, total; };
+struct TopkWs { size_t keys, flags, kept2, total; };
 static PostWs post_ws(long long total, int nseg) {
     PostWs w;
     size_t o = 0;
@@ -1150,6 +1379,32 @@ static PostWs post_ws(long long total, int nseg) {
     w.kpos = o; o = al16(o + t * 4);
     w.total = o;
     return w;
+}
+static PostExWs post_ex_ws(long long total, int nseg, bool soft) {
+    PostExWs w;
+    w.base = post_ws(total, nseg);
+    size_t o = w.base.total;
+    const size_t t = soft ? (size_t)(total > 0 ? total : 1) : 0;
+    w.w = o; o = al16(o + t * 4);
+    w.ew = o; o = al16(o + t * 4);
+    w.alive = o; o = al16(o + t);
+    w.total = o;
+    return w;
+}
+static TopkWs topk_ws(long long total, int nseg) {
+    TopkWs w;
+    size_t o = 0;
+    const size_t t = (size_t)(total > 0 ? total : 1);
+    w.keys = o; o = al16(o + t * 8);
+    w.flags = o; o = al16(o + t * 4);
+    w.kept2 = o; o = al16(o + (size_t)(nseg > 0 ? nseg : 1) * 4);
+    w.total = o;
+    return w;
+}
+static bool nms_opts_ok(const y4_nms_opts* o) {
+    return (o->metric == Y4_NMS_IOU || o->metric == Y4_NMS_DIOU) &&
+           (o->soft == Y4_SOFT_NONE || o->soft == Y4_SOFT_LINEAR || o->soft == Y4_SOFT_GAUSSIAN) &&
+           !(o->soft == Y4_SOFT_GAUSSIAN && !(o->sigma > 0.f)) && (o->agnostic == 0 || o->agnostic == 1) && o->max_det >= 0;
 }
 
 inline int grid_for(long long total) {
@@ -1371,24 +1626,32 @@ int y4_yolo_box_loss_bwd_f32(const float* pred, int box_kind, float gain, const 
     return Y4_OK;
 }
 
-int y4_post_count_f32(float* prediction, int B, long long N, int n_classes, float conf_thre,
-                      int convert_xyxy, int* counts, void* stream) {
+int y4_post_count_ex_f32(float* prediction, int B, long long N, int n_classes, float conf_thre,
+                         int convert_xyxy, int agnostic, int* counts, void* stream) {
     if (!prediction || !counts) return Y4_ERR_NULL;
-    if (B <= 0 || N <= 0 || n_classes <= 0) return Y4_ERR_SHAPE;
+    if (B <= 0 || N <= 0 || n_classes <= 0 || (agnostic != 0 && agnostic != 1)) return Y4_ERR_SHAPE;
+    if (agnostic && N * n_classes >= (1ll << 31)) return Y4_ERR_SHAPE;
     hipStream_t st = y4_stream(stream);
-    if (hipMemsetAsync(counts, 0, (size_t)B * n_classes * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
+    if (hipMemsetAsync(counts, 0, (size_t)B * (agnostic ? 1 : n_classes) * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
     const int pitch = (5 + n_classes) | 1;
     const size_t smem = (size_t)POST_ROWS * pitch * 4 + (size_t)2 * n_classes * 4;     // tile + the two histograms
     if (5 + n_classes <= POST_MAX_NCH && smem <= 65536) {                             // (64 KiB: the default dynamic-LDS limit)
         const long long ntiles = ((long long)B * N + POST_ROWS - 1) / POST_ROWS;
-        hipLaunchKernelGGL(post_count_tiled_kernel, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), smem, st,
+        auto kern = agnostic ? post_count_tiled_kernel<true> : post_count_tiled_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), smem, st,
                            prediction, B, N, n_classes, conf_thre, convert_xyxy, counts);
     } else {
-        hipLaunchKernelGGL(post_count_kernel, dim3(grid_for((long long)B * N)), dim3(256), 0, st, prediction, B, N,
+        auto kern = agnostic ? post_count_kernel<true> : post_count_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3(grid_for((long long)B * N)), dim3(256), 0, st, prediction, B, N,
                            n_classes, conf_thre, convert_xyxy, counts);
     }
     Y4_CHECK_LAUNCH();
     return Y4_OK;
+}
+
+int y4_post_count_f32(float* prediction, int B, long long N, int n_classes, float conf_thre,
+                      int convert_xyxy, int* counts, void* stream) {
+    return y4_post_count_ex_f32(prediction, B, N, n_classes, conf_thre, convert_xyxy, 0, counts, stream);
 }
 
 int y4_post_scan_i32(const int* counts, int n_segments, long long cap, int* seg_offsets, int* info, void* stream) {
@@ -1416,15 +1679,23 @@ size_t y4_post_nms_workspace(long long total_candidates, int n_segments) {
     return post_ws(total_candidates, n_segments).total;
 }
 
-int y4_post_nms_f32(const float* prediction, int B, long long N, int n_classes, float conf_thre,
-                    float nms_thre, const int* seg_offsets, long long total_candidates,
-                    float* det_rows, int* kept, void* workspace, size_t workspace_bytes, void* stream) {
-    if (!prediction || !seg_offsets || !det_rows || !kept || !workspace) return Y4_ERR_NULL;
+size_t y4_post_nms_ex_workspace(long long total_candidates, int n_segments, const y4_nms_opts* opts) {
+    if (!opts || !nms_opts_ok(opts)) return 0;
+    return post_ex_ws(total_candidates, n_segments, opts->soft != Y4_SOFT_NONE).total;
+}
+
+int y4_post_nms_ex_f32(const float* prediction, int B, long long N, int n_classes, float conf_thre, float nms_thre,
+                       const y4_nms_opts* opts, const int* seg_offsets, long long total_candidates,
+                       float* det_rows, int* kept, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!prediction || !opts || !seg_offsets || !det_rows || !kept || !workspace) return Y4_ERR_NULL;
     if (B <= 0 || N <= 0 || N >= (1ll << 31) || n_classes <= 0 || total_candidates < 0 ||
-        total_candidates >= (1ll << 31)) return Y4_ERR_SHAPE;
-    const int nseg = B * n_classes;
-    const PostWs l = post_ws(total_candidates, nseg);
-    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
+        total_candidates >= (1ll << 31) || !nms_opts_ok(opts)) return Y4_ERR_SHAPE;
+    const bool agn = opts->agnostic != 0, soft = opts->soft != Y4_SOFT_NONE, diou = opts->metric == Y4_NMS_DIOU;
+    if (agn && N * n_classes >= (1ll << 31)) return Y4_ERR_SHAPE;
+    const int nseg = agn ? B : B * n_classes;
+    const PostExWs lx = post_ex_ws(total_candidates, nseg, soft);
+    const PostWs& l = lx.base;
+    if (workspace_bytes < lx.total) return Y4_ERR_WORKSPACE;
     char* base = static_cast<char*>(workspace);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + l.keys);
     int* cursor = reinterpret_cast<int*>(base + l.cursor);
@@ -1434,16 +1705,68 @@ int y4_post_nms_f32(const float* prediction, int B, long long N, int n_classes, 
     const size_t smem = (size_t)POST_ROWS * pitch * 4;
     if (5 + n_classes <= POST_MAX_NCH && smem <= 65536) {
         const long long ntiles = ((long long)B * N + POST_ROWS - 1) / POST_ROWS;
-        hipLaunchKernelGGL(post_fill_tiled_kernel, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), smem, st,
+        auto kern = agn ? post_fill_tiled_kernel<true> : post_fill_tiled_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), smem, st,
                            prediction, B, N, n_classes, conf_thre, seg_offsets, cursor, keys);
     } else {
-        hipLaunchKernelGGL(post_fill_kernel, dim3(grid_for((long long)B * N)), dim3(256), 0, st, prediction, B, N,
+        auto kern = agn ? post_fill_kernel<true> : post_fill_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3(grid_for((long long)B * N)), dim3(256), 0, st, prediction, B, N,
                            n_classes, conf_thre, seg_offsets, cursor, keys);
     }
     Y4_CHECK_LAUNCH();
-    hipLaunchKernelGGL(post_nms_kernel, dim3(nseg), dim3(256), 0, st, prediction, N, n_classes, nms_thre, seg_offsets,
-                       keys, reinterpret_cast<float4*>(base + l.kbox), reinterpret_cast<float*>(base + l.karea),
-                       reinterpret_cast<int*>(base + l.kpos), det_rows, kept);
+    float4* kbox = reinterpret_cast<float4*>(base + l.kbox);
+    float* karea = reinterpret_cast<float*>(base + l.karea);
+    int* kpos = reinterpret_cast<int*>(base + l.kpos);
+    if (!soft) {
+        auto kern = diou ? (agn ? post_nms_kernel<Y4_NMS_DIOU, true> : post_nms_kernel<Y4_NMS_DIOU, false>)
+                         : (agn ? post_nms_kernel<Y4_NMS_IOU, true> : post_nms_kernel<Y4_NMS_IOU, false>);
+        hipLaunchKernelGGL(kern, dim3(nseg), dim3(256), 0, st, prediction, N, n_classes, nms_thre, opts->max_det, seg_offsets,
+                           keys, kbox, karea, kpos, det_rows, kept);
+    } else {
+        auto kern = diou ? (agn ? post_soft_nms_kernel<Y4_NMS_DIOU, true> : post_soft_nms_kernel<Y4_NMS_DIOU, false>)
+                         : (agn ? post_soft_nms_kernel<Y4_NMS_IOU, true> : post_soft_nms_kernel<Y4_NMS_IOU, false>);
+        hipLaunchKernelGGL(kern, dim3(nseg), dim3(256), 0, st, prediction, N, n_classes, nms_thre, opts->soft, opts->sigma,
+                           conf_thre, opts->max_det, seg_offsets, keys, kbox, karea, reinterpret_cast<float*>(base + lx.w),
+                           reinterpret_cast<unsigned char*>(base + lx.alive), kpos, reinterpret_cast<float*>(base + lx.ew),
+                           det_rows, kept);
+    }
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+
+int y4_post_nms_f32(const float* prediction, int B, long long N, int n_classes, float conf_thre,
+                    float nms_thre, const int* seg_offsets, long long total_candidates,
+                    float* det_rows, int* kept, void* workspace, size_t workspace_bytes, void* stream) {
+    y4_nms_opts opts = {};
+    opts.metric = Y4_NMS_IOU; opts.soft = Y4_SOFT_NONE; opts.sigma = 0.5f;
+    return y4_post_nms_ex_f32(prediction, B, N, n_classes, conf_thre, nms_thre, &opts, seg_offsets, total_candidates,
+                              det_rows, kept, workspace, workspace_bytes, stream);
+}
+
+size_t y4_post_topk_workspace(long long total_candidates, int n_segments) {
+    return topk_ws(total_candidates, n_segments).total;
+}
+
+int y4_post_topk_compact_f32(const float* det_rows, const int* seg_offsets, const int* kept, int B, int segs_per_image,
+                             int max_det, long long total_candidates, float* out_rows, int* out_offsets,
+                             int* img_offsets, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!det_rows || !seg_offsets || !kept || !out_rows || !out_offsets || !img_offsets || !workspace) return Y4_ERR_NULL;
+    if (B <= 0 || segs_per_image <= 0 || max_det <= 0 || total_candidates < 0 || total_candidates >= (1ll << 31) ||
+        (long long)B * segs_per_image >= (1ll << 31)) return Y4_ERR_SHAPE;
+    const int nseg = B * segs_per_image;
+    const TopkWs l = topk_ws(total_candidates, nseg);
+    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
+    char* base = static_cast<char*>(workspace);
+    int* flags = reinterpret_cast<int*>(base + l.flags);
+    int* kept2 = reinterpret_cast<int*>(base + l.kept2);
+    hipStream_t st = y4_stream(stream);
+    hipLaunchKernelGGL(post_topk_kernel, dim3(B), dim3(256), 0, st, det_rows, seg_offsets, kept, segs_per_image, max_det,
+                       reinterpret_cast<unsigned long long*>(base + l.keys), flags, kept2);
+    Y4_CHECK_LAUNCH();
+    hipLaunchKernelGGL(post_out_scan_kernel, dim3(1), dim3(1024), 0, st, kept2, nseg, segs_per_image, B, out_offsets, img_offsets);
+    Y4_CHECK_LAUNCH();
+    hipLaunchKernelGGL(post_compact_flagged_kernel, dim3(nseg), dim3(64), 0, st, det_rows, seg_offsets, kept, flags,
+                       out_offsets, out_rows);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }

@@ -10,6 +10,7 @@ Per batch the device work is a handful of launches, and the host waits twice: po
     python -m yolov4_amd.detect --cfg CFG --ckpt CKPT --source IMAGE_OR_DIR --dest runs/detect
 """
 import argparse
+import dataclasses
 import glob
 import json
 import os
@@ -21,7 +22,7 @@ from ._lib import Y4Error
 from .yolo.data.jpeg import decode_jpeg_batch
 from .yolo.data.jpeg_enc import encode_jpeg_batch
 from .yolo.data.transform import val_batch
-from .yolo.util.utils import postprocess, yolobox2yxyx
+from .yolo.util.utils import NMSOptions, postprocess, postprocess_nms, yolobox2yxyx
 from .yolo.util.vis import class_colors, draw_detections
 
 LINE_WIDTH = 3          # the reference's show_bbox
@@ -43,7 +44,8 @@ def _read(source):
 
 
 @torch.no_grad()
-def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None, draw=True, encode=True, batch=8):
+def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None, draw=True, encode=True, batch=8,
+                  nms_options=None):
     """sources: JPEG bytes, paths, or [h, w, 3] uint8 BGR device tensors, in any mix -> one dict per source:
       detections  float64 ndarray [n, 7]: (y1, x1, y2, x2, obj, cls_conf, cls) in SOURCE pixels, postprocess's order
       image       [h, w, 3] uint8 BGR device tensor of the source's size, the detections drawn on it when `draw`
@@ -51,7 +53,10 @@ def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None
       jpeg        that image as a JPEG file (cv2.imwrite's defaults: quality 95, 4:2:0) when `encode`, else None
     conf_thre / nms_thre default to cfg['TEST']['CONFTHRE'] / ['NMSTHRE'] (None or negative, the reference's rule).  The
     label is '<name> <cls_conf:.2f>'; without `names` the class index stands for the name.  The model is run in eval mode, in
-    batches of `batch` images, and left in eval mode."""
+    batches of `batch` images, and left in eval mode.  `nms_options` (an NMSOptions or a dict of postprocess_nms's keywords):
+    DIoU- / Soft- / class-agnostic NMS and the per-image cap; None is the reference's postprocess."""
+    if nms_options is not None and not isinstance(nms_options, dict):
+        nms_options = nms_options.kwargs()
     conf_thre = cfg['TEST']['CONFTHRE'] if conf_thre is None or conf_thre < 0 else conf_thre
     nms_thre = cfg['TEST']['NMSTHRE'] if nms_thre is None or nms_thre < 0 else nms_thre
     img_size = int(cfg['TEST']['IMGSIZE'])
@@ -77,7 +82,10 @@ def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None
                     raise Y4Error('source %d: a tensor source is a [h, w, 3] uint8 BGR device tensor' % (start + k))
                 images[k] = s.clone(memory_format=torch.contiguous_format)
         x, infos = val_batch(images, img_size)
-        dets = postprocess(model(x), num_classes, conf_thre=conf_thre, nms_thre=nms_thre)
+        if nms_options is None:
+            dets = postprocess(model(x), num_classes, conf_thre=conf_thre, nms_thre=nms_thre)
+        else:
+            dets = postprocess_nms(model(x), num_classes, conf_thre=conf_thre, nms_thre=nms_thre, **nms_options)
         # one device -> host copy for the whole batch (the rows of all images are slices of one tensor already)
         have = [d for d in dets if d is not None]
         rows = torch.cat(have).cpu().numpy().astype(np.float64) if have else np.zeros((0, 7))
@@ -127,9 +135,7 @@ def load_cfg(path):
         return yaml.safe_load(text)
 
 
-def main(argv=None):
-    from .yolo.model.yolov4 import YOLOv4
-    from .yolo.util.checkpoint import load_checkpoint
+def build_parser():
     ap = argparse.ArgumentParser(description='YOLOv4 detection on JPEG files')
     ap.add_argument('--cfg', required=True)
     ap.add_argument('--ckpt', default=None, help='a checkpoint in the reference format')
@@ -139,7 +145,37 @@ def main(argv=None):
     ap.add_argument('--conf-thre', type=float, default=-0.1)
     ap.add_argument('--nms-thre', type=float, default=-0.1)
     ap.add_argument('--batch', type=int, default=8)
-    args = ap.parse_args(argv)
+    # NMS options: a flag that is given overrides the cfg's TEST.NMS_METRIC / NMS_SOFT / NMS_SIGMA / NMS_AGNOSTIC / MAX_DET
+    ap.add_argument('--nms-metric', choices=['iou', 'diou'], default=None)
+    ap.add_argument('--soft-nms', choices=['none', 'linear', 'gaussian'], default=None)
+    ap.add_argument('--nms-sigma', type=float, default=None)
+    ap.add_argument('--agnostic-nms', action='store_true', default=None)
+    ap.add_argument('--max-det', type=int, default=None)
+    return ap
+
+
+def nms_options_from_args(args, cfg):
+    """The cfg's NMS options with the command line's on top; None when nothing asks for more than the reference's rule."""
+    o = NMSOptions.from_cfg(cfg)
+    over = {}
+    if args.nms_metric is not None:
+        over['metric'] = args.nms_metric
+    if args.soft_nms is not None:
+        over['soft'] = None if args.soft_nms == 'none' else args.soft_nms
+    if args.nms_sigma is not None:
+        over['sigma'] = args.nms_sigma
+    if args.agnostic_nms:
+        over['agnostic'] = True
+    if args.max_det is not None:
+        over['max_det'] = args.max_det
+    o = dataclasses.replace(o, **over)
+    return None if o == NMSOptions() else o
+
+
+def main(argv=None):
+    from .yolo.model.yolov4 import YOLOv4
+    from .yolo.util.checkpoint import load_checkpoint
+    args = build_parser().parse_args(argv)
     cfg = load_cfg(args.cfg)
     paths = [args.source] if os.path.isfile(args.source) else sorted(
         glob.glob(os.path.join(args.source, '*.jpg')) + glob.glob(os.path.join(args.source, '*.jpeg')))
@@ -151,7 +187,8 @@ def main(argv=None):
         load_checkpoint(model, args.ckpt)
     save_dir = increment_path(os.path.join(args.dest, 'exp'))
     os.makedirs(save_dir)
-    out = detect_images(model, cfg, paths, args.conf_thre, args.nms_thre, names=args.names, batch=args.batch)
+    out = detect_images(model, cfg, paths, args.conf_thre, args.nms_thre, names=args.names, batch=args.batch,
+                        nms_options=nms_options_from_args(args, cfg))
     for path, r in zip(paths, out):
         target = os.path.join(save_dir, os.path.splitext(os.path.basename(path))[0] + '.jpg')
         with open(target, 'wb') as f:

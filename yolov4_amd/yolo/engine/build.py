@@ -17,7 +17,7 @@ import torch.distributed as dist
 
 from ..optim.lr_schedulers.build import adjust_learning_rate
 from ... import trace
-from ..util.utils import detections_to_coco, postprocess
+from ..util.utils import detections_to_coco, postprocess, postprocess_nms
 
 
 class AverageMeter:
@@ -117,12 +117,17 @@ def _img_infos(info, batch):
 
 
 @torch.no_grad()
-def validate(val_loader, model, conf_threshold, nms_threshold, device=None, evaluator=None, num_classes=80):
+def validate(val_loader, model, conf_threshold, nms_threshold, device=None, evaluator=None, num_classes=80,
+             nms_options=None):
     """build.py:111-190.  Returns (AP50_95, AP50) from `evaluator(records, image_ids)` when one is given (the
     reference calls pycocotools' COCOeval there); without one returns (0, 0) like the reference's empty branch and
     leaves the COCO-format records on `validate.records`.  `yolo/util/cocoeval.py::COCOEvaluator(annotations)` is such an
     evaluator: the COCOeval protocol on the device.  Unlike the reference the loader may hand batches larger
-    than 1: target['img_info'] is then a list of per-image [h, w, S, S, id, ...] rows."""
+    than 1: target['img_info'] is then a list of per-image [h, w, S, S, id, ...] rows.  `nms_options` (an NMSOptions, or a
+    dict of postprocess_nms's keywords) selects DIoU- / Soft- / class-agnostic NMS and the per-image cap; None is the
+    reference's postprocess."""
+    if nms_options is not None and not isinstance(nms_options, dict):
+        nms_options = nms_options.kwargs()
     model.eval()
     ids, data_list = [], []
     class_ids = getattr(getattr(val_loader, 'dataset', None), 'class_ids', None)
@@ -132,7 +137,10 @@ def validate(val_loader, model, conf_threshold, nms_threshold, device=None, eval
         with trace.range('y4.eval_forward'):
             outputs = model(img.to(device) if device is not None else img)                        # :133
         with trace.range('y4.postprocess'):
-            outputs = postprocess(outputs, num_classes, conf_threshold, nms_threshold)            # :137
+            if nms_options is None:
+                outputs = postprocess(outputs, num_classes, conf_threshold, nms_threshold)        # :137
+            else:
+                outputs = postprocess_nms(outputs, num_classes, conf_threshold, nms_threshold, **nms_options)
         for det, info in zip(outputs, infos):
             id_ = int(info[-2])
             ids.append(id_)

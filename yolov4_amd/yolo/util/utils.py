@@ -7,14 +7,19 @@ reference's per-class device->host copies and its Python/numpy loops: candidate 
 sums, key fill, sort + NMS and compaction all run on the device.  Tie order is
 DEFINED here (score desc, then lower box index first); the reference's comes from an
 unstable numpy argsort and is platform dependent.
+
+postprocess_nms() is the same pipeline with a DIoU measure, Soft-NMS, class-agnostic
+segments and a per-image cap; postprocess() stays the reference's rule.
 """
 import ctypes
+import dataclasses
+from typing import Optional
 
 import numpy as np
 import torch
 
 from ... import ops
-from ..._lib import check, lib
+from ..._lib import NMS_METRICS, NMS_SOFT, NmsOpts, check, lib
 
 
 def _dev():
@@ -95,6 +100,112 @@ def postprocess(prediction, num_classes, conf_thre=0.7, nms_thre=0.45):
     if n_det == 0:
         return out
     dets = final[:n_det].clone()                                          # (lets the cap-sized buffers go)
+    if on_host:
+        dets = dets.cpu()
+    for b in range(B):
+        if img_off[b + 1] > img_off[b]:
+            out[b] = dets[img_off[b]:img_off[b + 1]]
+    return out
+
+
+@dataclasses.dataclass
+class NMSOptions:
+    """What postprocess_nms() takes beyond the two thresholds.  The defaults are the reference's rule."""
+    metric: str = 'iou'
+    soft: Optional[str] = None
+    sigma: float = 0.5
+    agnostic: bool = False
+    max_det: int = 0
+
+    def __post_init__(self):
+        if self.metric not in NMS_METRICS:
+            raise ValueError('metric: %r is not one of %s' % (self.metric, sorted(NMS_METRICS)))
+        if self.soft not in NMS_SOFT:
+            raise ValueError("soft: %r is not None, 'linear' or 'gaussian'" % (self.soft,))
+        if self.soft == 'gaussian' and not float(self.sigma) > 0:
+            raise ValueError('sigma must be positive')
+        if int(self.max_det) < 0:
+            raise ValueError('max_det must be >= 0 (0: no cap)')
+
+    @classmethod
+    def from_cfg(cls, cfg):
+        """cfg['TEST'] may hold NMS_METRIC, NMS_SOFT, NMS_SIGMA, NMS_AGNOSTIC, MAX_DET; a cfg without them gives the defaults"""
+        t = (cfg or {}).get('TEST', {}) or {}
+        soft = t.get('NMS_SOFT', None)
+        if soft in ('', 'none', 'None', False):
+            soft = None
+        return cls(metric=str(t.get('NMS_METRIC', 'iou')).lower(), soft=soft.lower() if isinstance(soft, str) else soft,
+                   sigma=float(t.get('NMS_SIGMA', 0.5)), agnostic=bool(t.get('NMS_AGNOSTIC', False)),
+                   max_det=int(t.get('MAX_DET', 0)))
+
+    def kwargs(self):
+        return dataclasses.asdict(self)
+
+
+def postprocess_nms(prediction, num_classes, conf_thre=0.7, nms_thre=0.45, *, metric='iou', soft=None, sigma=0.5,
+                    agnostic=False, max_det=0):
+    """postprocess() with options: metric 'iou' | 'diou', soft None | 'linear' | 'gaussian' (Soft-NMS,
+    `sigma` for the Gaussian decay), agnostic (all classes of an image compete), max_det (rows kept per image, 0: all).
+    Same return contract and in-place xyxy side effect; with the defaults the same kernels run and the result is
+    bit-identical.  Soft-NMS rows carry cls_conf * W, so row[4] * row[5] is the decayed score."""
+    o = NMSOptions(metric, soft, sigma, agnostic, max_det)
+    L = lib()
+    src = prediction
+    on_host = not prediction.is_cuda
+    if on_host:
+        prediction = prediction.to(_dev())
+    if prediction.dtype != torch.float32 or not prediction.is_contiguous():
+        raise ops.Y4Error('postprocess_nms expects a contiguous float32 [B,N,5+C] tensor')
+    B, N, n_ch = prediction.shape
+    if n_ch != 5 + num_classes:
+        raise ops.Y4Error('postprocess_nms: last dim must be 5 + num_classes')
+    dev = prediction.device
+    out = [None for _ in range(B)]
+    if N == 0 or B == 0:
+        return out
+    opts = NmsOpts(NMS_METRICS[o.metric], NMS_SOFT[o.soft], float(o.sigma), int(bool(o.agnostic)), int(o.max_det))
+    popts = ctypes.addressof(opts)
+    per_img = 1 if o.agnostic else num_classes
+    nseg = B * per_img
+    counts = torch.empty(nseg, dtype=torch.int32, device=dev)
+    st = ops._stream()
+    check(L.y4_post_count_ex_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), 1, opts.agnostic,
+                                 ops._ptr(counts), st), 'post_count_ex')
+    if on_host:
+        src[:, :, :4] = prediction[:, :, :4].cpu()
+    # as in postprocess(): everything stays on the device until the one host read of the per-image offsets
+    cap = int(min(B * N * num_classes, max(B * N // 2, 1 << 16), (1 << 31) - 1))
+    seg_off = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
+    meta = torch.empty(2 + B + 1, dtype=torch.int32, device=dev)          # [total, overflow | img_off[0..B]]
+    out_off = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
+    kept = torch.empty(nseg, dtype=torch.int32, device=dev)
+    while True:
+        check(L.y4_post_scan_i32(ops._ptr(counts), nseg, cap, ops._ptr(seg_off), ops._ptr(meta), st), 'post_scan')
+        rows = torch.empty((cap, 7), dtype=torch.float32, device=dev)
+        final = torch.empty((cap, 7), dtype=torch.float32, device=dev)
+        nbytes = L.y4_post_nms_ex_workspace(cap, nseg, popts)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        check(L.y4_post_nms_ex_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), float(nms_thre), popts,
+                                   ops._ptr(seg_off), cap, ops._ptr(rows), ops._ptr(kept), ops._ptr(ws), nbytes, st),
+              'post_nms_ex')
+        if o.max_det > 0:
+            tbytes = L.y4_post_topk_workspace(cap, nseg)
+            tws = torch.empty(tbytes, dtype=torch.uint8, device=dev)
+            check(L.y4_post_topk_compact_f32(ops._ptr(rows), ops._ptr(seg_off), ops._ptr(kept), B, per_img, int(o.max_det),
+                                             cap, ops._ptr(final), ops._ptr(out_off), ops._ptr(meta[2:]), ops._ptr(tws),
+                                             tbytes, st), 'post_topk_compact')
+        else:
+            check(L.y4_post_compact_f32(ops._ptr(rows), ops._ptr(seg_off), ops._ptr(kept), B, per_img, ops._ptr(final),
+                                        ops._ptr(out_off), ops._ptr(meta[2:]), st), 'post_compact')
+        host = meta.cpu().numpy().astype(np.int64)                        # the host sync
+        if not host[1]:
+            break
+        cap = int(host[0])
+    img_off = host[2:]
+    n_det = int(img_off[B])
+    if n_det == 0:
+        return out
+    dets = final[:n_det].clone()
     if on_host:
         dets = dets.cpu()
     for b in range(B):
