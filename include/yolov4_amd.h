@@ -382,6 +382,23 @@ int y4_yolo_decode_eval_f32(const float* logits, int ldl, float* out, long long 
 int y4_yolo_decode_bwd_f32(const float* logits, int ldl, const float* g_output, const float* g_pred,
                            float* g_logits, int B, int F, int A, int n_classes,
                            const float* anchors_wh_host, void* stream);
+/* The same three with the YOLOv4 grid-sensitivity factor scale_x_y (Darknet's [yolo] scale_x_y: 1.2 / 1.1 / 1.05 per
+ * layer, 2.0 in the scaled models).  s = scale_xy as fp32, h = (s - 1) * 0.5f in fp32, sigma = the fp32 sigmoid:
+ *   train: pred[..., 0] = ((sigma_x * s) - h) + i, pred[..., 1] = ((sigma_y * s) - h) + j; output[..., 0:2] stays sigma.
+ *   eval : the same centre, times stride.  The tiled kernel evaluates sigma * (s * stride) + stride * (i - h), and
+ *          sigma * s + (i - h) in training: other roundings, the same value to a few ulp of its largest addend.
+ *   bwd  : the g_pred contribution on channels 0 and 1 is s * g_pred.
+ * w, h, objectness and classes are untouched.  scale_xy = 1 gives the bits of the entries above (sigma * 1 and x - 0 are
+ * exact), which forward here.  scale_xy outside [1, 2], NaN included: Y4_ERR_SHAPE before any launch. */
+int y4_yolo_decode_train_ex_f32(const float* logits, int ldl, float* output, float* pred,
+                                int B, int F, int A, int n_classes, const float* anchors_wh_host, float scale_xy,
+                                void* stream);
+int y4_yolo_decode_eval_ex_f32(const float* logits, int ldl, float* out, long long n_total, long long box_off,
+                               int B, int F, int A, int n_classes, const float* anchors_wh_host,
+                               float stride, float scale_xy, void* stream);
+int y4_yolo_decode_bwd_ex_f32(const float* logits, int ldl, const float* g_output, const float* g_pred,
+                              float* g_logits, int B, int F, int A, int n_classes,
+                              const float* anchors_wh_host, float scale_xy, void* stream);
 
 /* ---------------------------------------------------------------- detection loss
  * Replaces YOLOLoss.build_target + YOLOLoss.forward for one layer,
@@ -438,6 +455,50 @@ int y4_yolo_box_loss_fwd_f32(const float* pred, int box_kind, float gain, int B,
 int y4_yolo_box_loss_bwd_f32(const float* pred, int box_kind, float gain, const float* gscale, float* g_output,
                              int B, int F, int A, int K, int n_classes,
                              const void* workspace, size_t workspace_bytes, void* stream);
+
+/* YOLOv4 head options of the loss (Darknet's [yolo] iou_thresh and label_smooth_eps; scale_x_y for the box gradient).
+ * Every entry above has an _ex form below that takes the options it depends on; the entries above forward to them with
+ * iou_thresh = 1, label_smooth = 0, scale_xy = 1 and give the bits they always gave.  The options are not stored in the
+ * workspace: pass to every later call the SAME iou_thresh and label_smooth that y4_yolo_loss_fwd_ex_f32 got.
+ *
+ * iou_thresh in (0, 1]; 1 = off.  Below 1, the positive anchors of a label are its arg-max anchor and every anchor k
+ *   whose shape IoU (the fp32 value the arg-max is taken over) is > iou_thresh -- strict; a NaN IoU never is.  In the
+ *   layer whose mask holds k the record's anchor slot is the place of k in the mask (anch_mask_host[a] % 3 == a is
+ *   required below 1).  The (label, slot) pairs of a layer go through the steps of the single pair -- skip outside the
+ *   map, find or create the cell's record, write the targets and the truth box (last writer wins), OR the class bit -- in
+ *   the order of the label index t, then of the slot a; records are numbered by first hit in that order, which fixes the
+ *   summation order of the box loss.  Record capacity per image: K with iou_thresh = 1 (the layout of
+ *   y4_yolo_loss_workspace), K * A below 1: pos_cell, pos_val, pos_cls and pos_box grow, y4_yolo_loss_workspace_ex says
+ *   by how much (it returns 0 for arguments out of range).
+ * label_smooth in [0, 1): class BCE targets are 1 - 0.5 * label_smooth where the class bit is set and 0.5 * label_smooth
+ *   where it is not (both fp32), in the loss forward, its backward and the dense targets (target[..., 5:] of positive
+ *   cells; 0 elsewhere).  Objectness is not smoothed.
+ * scale_xy in [1, 2] (box-loss backward only): channels 0 and 1 become (*gscale) * gain * scale_xy * dL/dp{x,y}, since
+ *   d pred / d output = scale_xy there.  The forward needs nothing: it reads the scaled centres from `pred`.
+ * Errors before any launch: NULL pointer Y4_ERR_NULL; an option or a shape out of range (NaN included) Y4_ERR_SHAPE;
+ * workspace_bytes < y4_yolo_loss_workspace_ex(.., iou_thresh) Y4_ERR_WORKSPACE. */
+size_t y4_yolo_loss_workspace_ex(int B, int F, int A, int K, int n_classes, float iou_thresh);
+int y4_yolo_loss_fwd_ex_f32(const float* output, const float* pred, const float* labels, int K,
+                            int B, int F, int A, int n_classes, float stride, float ignore_thresh,
+                            const float* all_anchors_host, int n_all_anchors, const int* anch_mask_host,
+                            float iou_thresh, float label_smooth, float* obj_mask, double* loss_parts,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int y4_yolo_loss_bwd_ex_f32(const float* output, int output_is_masked, const float* obj_mask,
+                            const float* gscale, float* g_output,
+                            int B, int F, int A, int K, int n_classes, float iou_thresh, float label_smooth,
+                            const void* workspace, size_t workspace_bytes, void* stream);
+int y4_yolo_loss_mask_output_ex_f32(float* output, const float* obj_mask, int B, int F, int A, int K,
+                                    int n_classes, float iou_thresh, const void* workspace, size_t workspace_bytes,
+                                    void* stream);
+int y4_yolo_loss_dense_targets_ex_f32(float* target, float* tgt_mask, float* tgt_scale,
+                                      int B, int F, int A, int K, int n_classes, float iou_thresh, float label_smooth,
+                                      const void* workspace, size_t workspace_bytes, void* stream);
+int y4_yolo_box_loss_fwd_ex_f32(const float* pred, int box_kind, float gain, int B, int F, int A, int K, int n_classes,
+                                float iou_thresh, double* loss_parts, const void* workspace, size_t workspace_bytes,
+                                void* stream);
+int y4_yolo_box_loss_bwd_ex_f32(const float* pred, int box_kind, float gain, const float* gscale, float* g_output,
+                                int B, int F, int A, int K, int n_classes, float iou_thresh, float scale_xy,
+                                const void* workspace, size_t workspace_bytes, void* stream);
 
 /* Device-side prefix sums of postprocess (no host round trip between its stages):
  * y4_post_scan_i32: seg_offsets[0..n_segments] = exclusive scan of the candidate counts, clamped to `cap` (the capacity, in

@@ -90,6 +90,16 @@ PROTOTYPES = {
     'y4_yolo_loss_dense_targets_f32': (I, [P, P, P, I, I, I, I, I, P, Z, P]),
     'y4_yolo_box_loss_fwd_f32': (I, [P, I, F, I, I, I, I, I, P, P, Z, P]),
     'y4_yolo_box_loss_bwd_f32': (I, [P, I, F, P, P, I, I, I, I, I, P, Z, P]),
+    'y4_yolo_decode_train_ex_f32': (I, [P, I, P, P, I, I, I, I, P, F, P]),
+    'y4_yolo_decode_eval_ex_f32': (I, [P, I, P, L, L, I, I, I, I, P, F, F, P]),
+    'y4_yolo_decode_bwd_ex_f32': (I, [P, I, P, P, P, I, I, I, I, P, F, P]),
+    'y4_yolo_loss_workspace_ex': (Z, [I, I, I, I, I, F]),
+    'y4_yolo_loss_fwd_ex_f32': (I, [P, P, P, I, I, I, I, I, F, F, P, I, P, F, F, P, P, P, Z, P]),
+    'y4_yolo_loss_bwd_ex_f32': (I, [P, I, P, P, P, I, I, I, I, I, F, F, P, Z, P]),
+    'y4_yolo_loss_mask_output_ex_f32': (I, [P, P, I, I, I, I, I, F, P, Z, P]),
+    'y4_yolo_loss_dense_targets_ex_f32': (I, [P, P, P, I, I, I, I, I, F, F, P, Z, P]),
+    'y4_yolo_box_loss_fwd_ex_f32': (I, [P, I, F, I, I, I, I, I, F, P, P, Z, P]),
+    'y4_yolo_box_loss_bwd_ex_f32': (I, [P, I, F, P, P, I, I, I, I, I, F, F, P, Z, P]),
     'y4_post_count_f32': (I, [P, I, L, I, F, I, P, P]),
     'y4_post_scan_i32': (I, [P, I, L, P, P, P]),
     'y4_post_compact_f32': (I, [P, P, P, I, I, P, P, P, P]),

@@ -25,7 +25,8 @@ template <bool EVAL>
 __global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restrict__ logits, long long ldl,
                                                           float* __restrict__ output, float* __restrict__ pred,
                                                           long long n_total, long long box_off, float stride,
-                                                          int B, int F, int A, int n_ch, Anchors anc) {
+                                                          int B, int F, int A, int n_ch, Anchors anc,
+                                                          float sxy, float hxy) {
     const long long npix = (long long)B * F * F;
     const int nt = A * n_ch;
     for (int t = threadIdx.x; t < nt; t += blockDim.x) {
@@ -37,8 +38,9 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restric
             const float v = logits[p * ldl + t];
             float o = v, pv = v;
             if (ch != 2 && ch != 3) { o = sigmoidf_(v); pv = o; }
-            if (ch == 0) pv = o + (float)i;
-            else if (ch == 1) pv = o + (float)j;
+            // scale_x_y: ((o * s) - h) + i, h = (s - 1) / 2.  s = 1: o * 1 and o - 0 are exact, the bits of o + i
+            if (ch == 0) pv = ((o * sxy) - hxy) + (float)i;
+            else if (ch == 1) pv = ((o * sxy) - hxy) + (float)j;
             else if (ch == 2) pv = expf(v) * anc.w[a];
             else if (ch == 3) pv = expf(v) * anc.h[a];
             if (EVAL) {
@@ -64,11 +66,15 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restric
 // segments per pixel (0.22 of the HBM peak) and spent 30 VALU per element on IEEE expf + division; this one moves whole
 // lines both ways with one v_exp_f32 + one v_rcp_f32 per element (~1e-7 relative, far inside the 1e-4 parity bar):
 // 4.6 - 4.9 TB/s algorithmic on the 76 x 76 layer at bs = 32 (rows of 32 pixels; 16 on small maps for occupancy).
-template <bool EVAL, int DEC_TP>                           // DEC_TP pixels per tile: DEC_TP x 256 floats of LDS
+// SCALED: scale_x_y != 1.  The instance without it has s = 1, h = 0 folded away at compile time: the default path runs the
+// code it always ran (a run-time s = 1 gave the same bits but measured 6 % slower in the eval decode of bench.py).
+template <bool EVAL, int DEC_TP, bool SCALED>              // DEC_TP pixels per tile: DEC_TP x 256 floats of LDS
 __global__ __launch_bounds__(256) void yolo_decode_tiled_kernel(const float* __restrict__ logits, long long ldl,
                                                                 float* __restrict__ output, float* __restrict__ pred,
                                                                 long long n_total, long long box_off, float stride,
-                                                                int F, int A, int n_ch, Anchors anc, int tiles_per_img) {
+                                                                int F, int A, int n_ch, Anchors anc, int tiles_per_img,
+                                                                float sxy_arg, float hxy_arg) {
+    const float sxy = SCALED ? sxy_arg : 1.0f, hxy = SCALED ? hxy_arg : 0.0f;
     __shared__ __attribute__((aligned(16))) float tile[DEC_TP][256];
     __shared__ __attribute__((aligned(16))) float predt[EVAL ? 1 : 4][DEC_TP][4];      // train: decoded boxes per anchor
     const int tid = threadIdx.x;
@@ -77,8 +83,10 @@ __global__ __launch_bounds__(256) void yolo_decode_tiled_kernel(const float* __r
     const int p0 = t * DEC_TP;
     const int cnt = FF - p0 < DEC_TP ? FF - p0 : DEC_TP;
     const int nt = A * n_ch;
-    // ---- phase 1.  Per column (fixed for the thread): value = rcp(exp(-v) + one) * mul + (ci * i + cj * j)
+    // ---- phase 1.  Per column (fixed for the thread): value = rcp(exp(-v) + one) * mul + (ci * (i - h) + cj * (j - h))
     //   sigmoid channels: one = 1 (1 / (1 + e^-v)); exp channels (w, h): one = 0 (1 / e^-v = e^v), mul = anchor (* stride)
+    //   x / y with scale_x_y = s: mul = s (* stride), h = (s - 1) / 2 taken off the cell index once per pixel row; s = 1
+    //   gives mul = 1 (* stride) and i - 0 = i: the bits of the form without the option, at its instruction count
     // -> one v_exp, one v_rcp and three plain VALU per element, no per-element role tests
     const int col4 = tid & 63, r0 = tid >> 6;
     f32x4 one, mul, ci, cj;
@@ -91,7 +99,7 @@ __global__ __launch_bounds__(256) void yolo_decode_tiled_kernel(const float* __r
         ca[e] = a; cch[e] = ch;
         const float sc = (EVAL && ch < 4) ? stride : 1.0f;
         one[e] = (ch == 2 || ch == 3) ? 0.f : 1.f;
-        mul[e] = ch == 2 ? anc.w[a < 0 ? 0 : a] * sc : ch == 3 ? anc.h[a < 0 ? 0 : a] * sc : sc;
+        mul[e] = ch == 2 ? anc.w[a < 0 ? 0 : a] * sc : ch == 3 ? anc.h[a < 0 ? 0 : a] * sc : ch < 2 ? sxy * sc : sc;
         ci[e] = ch == 0 ? sc : 0.f;
         cj[e] = ch == 1 ? sc : 0.f;
     }
@@ -110,7 +118,7 @@ __global__ __launch_bounds__(256) void yolo_decode_tiled_kernel(const float* __r
         if (r >= cnt) break;
         const int pix = p0 + r;
         const int j = pix / F, i = pix - j * F;
-        const float fi = (float)i, fj = (float)j;
+        const float fi = (float)i - hxy, fj = (float)j - hxy;
         const f32x4 v = vv[u];
         f32x4 o;
 #pragma unroll
@@ -181,7 +189,7 @@ __global__ __launch_bounds__(256) void yolo_decode_bwd_kernel(const float* __res
                                                               const float* __restrict__ g_out,
                                                               const float* __restrict__ g_pred,
                                                               float* __restrict__ g_logits,
-                                                              int B, int F, int A, int n_ch, Anchors anc) {
+                                                              int B, int F, int A, int n_ch, Anchors anc, float sxy) {
     const long long npix = (long long)B * F * F;
     const int nt = A * n_ch;
     for (int t = threadIdx.x; t < (int)ldl; t += blockDim.x) {
@@ -197,7 +205,7 @@ __global__ __launch_bounds__(256) void yolo_decode_bwd_kernel(const float* __res
                 if (g_out) g = g_out[cell * n_ch + ch];
                 if (ch < 4 && g_pred) {
                     const float gp = g_pred[cell * 4 + ch];
-                    if (ch < 2) g += gp;
+                    if (ch < 2) g += sxy * gp;                    // d pred / d output = scale_x_y (1 * gp is exact)
                     else g += gp * (expf(v) * (ch == 2 ? anc.w[a] : anc.h[a]));
                 }
                 if (ch != 2 && ch != 3) {
@@ -249,7 +257,14 @@ struct LossWs {
 };
 static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr int LOSS_BLOCK = 256;
-static LossWs loss_ws(int B, int F, int A, int K, int C) {
+// R: records an image can hold per layer.  One positive anchor per label (iou_thresh >= 1): R = K.  Several (iou_thresh
+// < 1): every label can be positive on each of the layer's A anchors, R = K * A.  With R = K the layout is unchanged.
+static inline int loss_rec_cap(int K, int A, float iou_thresh) { return iou_thresh < 1.f ? K * A : K; }
+static inline bool loss_opts_ok(float iou_thresh, float label_smooth) {          // false for NaN too
+    return iou_thresh > 0.f && iou_thresh <= 1.f && label_smooth >= 0.f && label_smooth < 1.f;
+}
+static inline bool scale_xy_ok(float s) { return s >= 1.f && s <= 2.f; }
+static LossWs loss_ws(int B, int F, int A, int K, int C, int R) {
     LossWs w;
     w.cw = (C + 31) / 32;
     const long long cells = (long long)B * A * F * F;
@@ -258,12 +273,12 @@ static LossWs loss_ws(int B, int F, int A, int K, int C) {
     w.nlabel = o; o = al16(o + (size_t)B * 4);
     w.npos = o; o = al16(o + (size_t)B * 4);
     w.truth = o; o = al16(o + (size_t)B * K * 4 * 4);
-    w.pos_cell = o; o = al16(o + (size_t)B * K * 4);
-    w.pos_val = o; o = al16(o + (size_t)B * K * 5 * 4);
-    w.pos_cls = o; o = al16(o + (size_t)B * K * w.cw * 4);
+    w.pos_cell = o; o = al16(o + (size_t)B * R * 4);
+    w.pos_val = o; o = al16(o + (size_t)B * R * 5 * 4);
+    w.pos_cls = o; o = al16(o + (size_t)B * R * w.cw * 4);
     w.pos_index = o; o = al16(o + (size_t)cells * 4);
     w.partials = o; o = al16(o + (size_t)w.nblocks * 4 * 8);
-    w.pos_box = o; o = al16(o + (size_t)B * K * 4 * 4);       // appended: every offset above is what it was without it
+    w.pos_box = o; o = al16(o + (size_t)B * R * 4 * 4);       // appended: every offset above is what it was without it
     w.total = o;
     return w;
 }
@@ -291,9 +306,15 @@ static LossPtrs loss_ptrs(const void* ws, const LossWs& l) {
 // yololoss.py:196-265,304-369: one thread per image walks its <= K labels in order (the
 // sequential semantics -- last writer wins for xy/wh/scale, class bits OR -- are kept by
 // construction); cost is negligible (B*K*9 IoUs).
-__global__ void yolo_assign_kernel(const float* __restrict__ labels, int K, int B, int F, int A, int C, int cw,
+//
+// MULTI (iou_thresh < 1, Darknet's iou_thresh): the positive anchors of a label are its arg-max anchor and every anchor
+// whose shape IoU is > iou_thresh (strict; a NaN IoU never is).  The (label, anchor slot) pairs of a layer go through the
+// steps of the single pair in the order of t, then of the slot a; records (R = K * A per image) are numbered by first hit
+// in that order.  The host only takes masks with mask[a] % 3 == a here, so the arg-max's slot best % 3 is its position.
+template <bool MULTI>
+__global__ void yolo_assign_kernel(const float* __restrict__ labels, int K, int R, int B, int F, int A, int C, int cw,
                                    float stride, Anchors all_anc, int n_all, int m0, int m1, int m2,
-                                   Anchors masked, LossPtrs w) {
+                                   Anchors masked, float iou_thresh, LossPtrs w) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const float* lab = labels + (long long)b * K * 5;
@@ -313,6 +334,7 @@ __global__ void yolo_assign_kernel(const float* __restrict__ labels, int K, int 
         // IoU of (0,0,tw,th) against the n_all anchors (0,0,aw,ah), xyxy form, first max wins
         int best = 0;
         float best_iou = -INFINITY;
+        float im0 = 0.f, im1 = 0.f, im2 = 0.f;                 // the IoU against the layer's own three anchors
         bool first = true;
         for (int k = 0; k < n_all; ++k) {
             const float aw = all_anc.w[k], ah = all_anc.h[k];
@@ -322,31 +344,39 @@ __global__ void yolo_assign_kernel(const float* __restrict__ labels, int K, int 
             const float iou = ai / ((tw * th + aw * ah) - ai);
             // torch.argmax: NaN counts as maximal; first occurrence wins
             if (first || iou > best_iou || (iou != iou && !(best_iou != best_iou))) { best = k; best_iou = iou; first = false; }
+            if (k == m0) im0 = iou;
+            if (k == m1) im1 = iou;
+            if (k == m2) im2 = iou;
         }
-        if (!(best == m0 || best == m1 || best == m2)) continue;
-        const int a = best % 3;
+        const bool best_here = best == m0 || best == m1 || best == m2;
+        if (!MULTI && !best_here) continue;
         const int i = (int)(short)(int)tx, j = (int)(short)(int)ty;                    // .to(torch.int16): truncation
-        if (i < 0 || i >= F || j < 0 || j >= F || a >= A) continue;          // reference would raise / wrap: skipped
-        const int cell = (a * F + j) * F + i;
-        int rec = -1;
-        for (int u = 0; u < np; ++u)
-            if (w.pos_cell[(long long)b * K + u] == cell) { rec = u; break; }
-        if (rec < 0) {
-            rec = np++;
-            w.pos_cell[(long long)b * K + rec] = cell;
-            for (int q = 0; q < cw; ++q) w.pos_cls[((long long)b * K + rec) * cw + q] = 0u;
-            w.pos_index[(long long)b * A * F * F + cell] = rec;
-        }
-        float* pv = w.pos_val + ((long long)b * K + rec) * 5;
-        pv[0] = tx - (float)(short)(int)tx;
-        pv[1] = ty - (float)(short)(int)ty;
-        pv[2] = logf(tw / masked.w[a] + 1e-16f);
-        pv[3] = logf(th / masked.h[a] + 1e-16f);
-        pv[4] = sqrtf(2.0f - tw * th / Ff / Ff);
-        float* pb = w.pos_box + ((long long)b * K + rec) * 4;                // last writer wins, like pv
-        pb[0] = tx; pb[1] = ty; pb[2] = tw; pb[3] = th;
+        if (i < 0 || i >= F || j < 0 || j >= F) continue;                    // reference would raise / wrap: skipped
         const int cls = (int)(short)(int)lab[t * 5 + 4];
-        if (cls >= 0 && cls < C) w.pos_cls[((long long)b * K + rec) * cw + (cls >> 5)] |= 1u << (cls & 31);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const int mk = a == 0 ? m0 : a == 1 ? m1 : m2;
+            const float ia = a == 0 ? im0 : a == 1 ? im1 : im2;
+            const bool hit = MULTI ? (mk == best || ia > iou_thresh) : (a == best % 3);
+            if (!hit || a >= A) continue;
+            const int cell = (a * F + j) * F + i;
+            int rec = w.pos_index[(long long)b * A * F * F + cell];         // -1 (the host's memset) until a pair hits the cell
+            if (rec < 0) {
+                rec = np++;
+                w.pos_cell[(long long)b * R + rec] = cell;
+                for (int q = 0; q < cw; ++q) w.pos_cls[((long long)b * R + rec) * cw + q] = 0u;
+                w.pos_index[(long long)b * A * F * F + cell] = rec;
+            }
+            float* pv = w.pos_val + ((long long)b * R + rec) * 5;
+            pv[0] = tx - (float)(short)(int)tx;
+            pv[1] = ty - (float)(short)(int)ty;
+            pv[2] = logf(tw / (a == 0 ? masked.w[0] : a == 1 ? masked.w[1] : masked.w[2]) + 1e-16f);
+            pv[3] = logf(th / (a == 0 ? masked.h[0] : a == 1 ? masked.h[1] : masked.h[2]) + 1e-16f);
+            pv[4] = sqrtf(2.0f - tw * th / Ff / Ff);
+            float* pb = w.pos_box + ((long long)b * R + rec) * 4;            // last writer wins, like pv
+            pb[0] = tx; pb[1] = ty; pb[2] = tw; pb[3] = th;
+            if (cls >= 0 && cls < C) w.pos_cls[((long long)b * R + rec) * cw + (cls >> 5)] |= 1u << (cls & 31);
+        }
     }
     w.npos[b] = np;
 }
@@ -427,6 +457,129 @@ __global__ __launch_bounds__(64) void yolo_assign_wave_kernel(const float* __res
     if (t == 0) w.npos[b] = __popcll(om);
 }
 
+// The wave form with several positive anchors per label (iou_thresh < 1; the kernel above stays as it is for the default
+// path, where it measured 2 us per call faster than a one-round instance of this one).  The three anchor slots are three
+// independent rounds of the same rules (a cell includes its slot, so labels collide only within a round); a record's
+// number is the count of owner (label, slot) pairs before its own in (t, a) order, from the three owner ballots.  Every
+// per-round array below is indexed by fully unrolled loops only (registers, no scratch).
+__global__ __launch_bounds__(64) void yolo_assign_wave_multi_kernel(const float* __restrict__ labels, int K, int R, int B,
+                                                                    int F, int A, int C, int cw, float stride,
+                                                                    Anchors all_anc, int n_all, int m0, int m1, int m2,
+                                                                    Anchors masked, float iou_thresh, LossPtrs w) {
+    constexpr int NR = 3;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const float* lab = labels + (long long)b * K * 5;
+    float l0 = 0.f, l1 = 0.f, l2 = 0.f, l3 = 0.f, l4 = 0.f;
+    if (t < K) { l0 = lab[t * 5]; l1 = lab[t * 5 + 1]; l2 = lab[t * 5 + 2]; l3 = lab[t * 5 + 3]; l4 = lab[t * 5 + 4]; }
+    const float s = (((l0 + l1) + l2) + l3) + l4;
+    const int n = __popcll(__ballot(t < K && s > 0.f));
+    if (t == 0) w.nlabel[b] = n;
+    const bool act = t < n;
+    const float tx = l0 / stride, ty = l1 / stride, tw = l2 / stride, th = l3 / stride;
+    if (act) {
+        float* tr = w.truth + ((long long)b * K + t) * 4;
+        tr[0] = tx; tr[1] = ty; tr[2] = tw; tr[3] = th;
+    }
+    int best = 0;
+    float best_iou = -INFINITY;
+    float im0 = 0.f, im1 = 0.f, im2 = 0.f;                     // the IoU against the layer's own three anchors
+    bool first = true;
+    for (int k = 0; k < n_all; ++k) {
+        const float aw = all_anc.w[k], ah = all_anc.h[k];
+        const float brx = fminf(tw, aw), bry = fminf(th, ah);
+        const float en = (0.f < brx && 0.f < bry) ? 1.f : 0.f;
+        const float ai = (brx * bry) * en;
+        const float iou = ai / ((tw * th + aw * ah) - ai);
+        if (first || iou > best_iou || (iou != iou && !(best_iou != best_iou))) { best = k; best_iou = iou; first = false; }
+        if (k == m0) im0 = iou;
+        if (k == m1) im1 = iou;
+        if (k == m2) im2 = iou;
+    }
+    const int i = (int)(short)(int)tx, j = (int)(short)(int)ty;
+    const bool inmap = act && i >= 0 && i < F && j >= 0 && j < F;
+    const int cls = (int)(short)(int)l4;
+    int slot[NR], cell[NR], owner[NR];
+    bool pos[NR], later_same[NR];
+    unsigned long long pm[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const int mk = r == 0 ? m0 : r == 1 ? m1 : m2;
+        const float ir = r == 0 ? im0 : r == 1 ? im1 : im2;
+        slot[r] = r;
+        pos[r] = inmap && r < A && (mk == best || ir > iou_thresh);
+        cell[r] = pos[r] ? (slot[r] * F + j) * F + i : -1 - t;               // non-positive lanes never match anyone
+        pm[r] = __ballot(pos[r]);
+        owner[r] = t;
+        later_same[r] = false;
+    }
+    for (int u = 0; u < 64; ++u) {
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const int cu = __shfl(cell[r], u, 64);
+            if (((pm[r] >> u) & 1ull) && cu == cell[r]) {
+                if (u < owner[r]) owner[r] = u;
+                if (u > t) later_same[r] = true;
+            }
+        }
+    }
+    bool is_owner[NR];
+    unsigned long long om[NR];
+    int before = 0;                                            // owner pairs of the labels before t, over all rounds
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        is_owner[r] = pos[r] && owner[r] == t;
+        om[r] = __ballot(is_owner[r]);
+        before += __popcll(om[r] & ((1ull << t) - 1ull));
+    }
+    int rec[NR];
+    int mine = 0;                                              // owner pairs of label t in the rounds before r
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const int my_rank = before + mine;
+        rec[r] = __shfl(my_rank, owner[r], 64);
+        mine += is_owner[r] ? 1 : 0;
+    }
+    for (int q = 0; q < cw; ++q) {
+        unsigned word[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) word[r] = 0u;
+        for (int u = 0; u < 64; ++u) {
+            const int ku = __shfl(cls, u, 64);
+            const bool kq = ku >= 0 && ku < C && (ku >> 5) == q;
+#pragma unroll
+            for (int r = 0; r < NR; ++r) {
+                const int cu = __shfl(cell[r], u, 64);
+                if (((pm[r] >> u) & 1ull) && cu == cell[r] && kq) word[r] |= 1u << (ku & 31);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            if (is_owner[r]) w.pos_cls[((long long)b * R + rec[r]) * cw + q] = word[r];
+    }
+    int np = 0;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        if (is_owner[r]) {
+            w.pos_cell[(long long)b * R + rec[r]] = cell[r];
+            w.pos_index[(long long)b * A * F * F + cell[r]] = rec[r];
+        }
+        if (pos[r] && !later_same[r]) {
+            const float Ff = (float)F;
+            const int a = slot[r];
+            float* pv = w.pos_val + ((long long)b * R + rec[r]) * 5;
+            pv[0] = tx - (float)(short)(int)tx;
+            pv[1] = ty - (float)(short)(int)ty;
+            pv[2] = logf(tw / masked.w[a] + 1e-16f);
+            pv[3] = logf(th / masked.h[a] + 1e-16f);
+            pv[4] = sqrtf(2.0f - tw * th / Ff / Ff);
+            float* pb = w.pos_box + ((long long)b * R + rec[r]) * 4;
+            pb[0] = tx; pb[1] = ty; pb[2] = tw; pb[3] = th;
+        }
+        np += __popcll(om[r]);
+    }
+    if (t == 0) w.npos[b] = np;
+}
+
 __device__ __forceinline__ float bce_term(float o, float t) {
     const float lo = fmaxf(logf(o), -100.f), l1 = fmaxf(logf(1.0f - o), -100.f);
     return -(t * lo + (1.0f - t) * l1);
@@ -435,8 +588,8 @@ __device__ __forceinline__ float bce_grad(float o, float t) { return (o - t) / f
 
 // yololoss.py:276-301 (ignore mask) + :402-427 (loss terms), one thread per cell.
 __global__ __launch_bounds__(LOSS_BLOCK) void yolo_loss_dense_kernel(
-    const float* __restrict__ output, const float* __restrict__ pred, int B, int F, int A, int K, int C, int cw,
-    float thresh, float* __restrict__ obj_mask, LossPtrs w) {
+    const float* __restrict__ output, const float* __restrict__ pred, int B, int F, int A, int K, int R, int C, int cw,
+    float thresh, float cls_lo, float cls_hi, float* __restrict__ obj_mask, LossPtrs w) {
     __shared__ double red[4][LOSS_BLOCK / 64];
     const long long cells = (long long)B * A * F * F;
     const long long cell = (long long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
@@ -471,15 +624,15 @@ __global__ __launch_bounds__(LOSS_BLOCK) void yolo_loss_dense_kernel(
         const float* o = output + cell * n_ch;
         if (m != 0.f) part[2] = (double)bce_term(o[4], rec >= 0 ? 1.f : 0.f);
         if (rec >= 0) {
-            const float* pv = w.pos_val + ((long long)b * K + rec) * 5;
-            const unsigned* pc = w.pos_cls + ((long long)b * K + rec) * cw;
+            const float* pv = w.pos_val + ((long long)b * R + rec) * 5;
+            const unsigned* pc = w.pos_cls + ((long long)b * R + rec) * cw;
             const float s = pv[4];
             const float ww = s * s;
             part[0] = (double)(ww * bce_term(o[0], pv[0])) + (double)(ww * bce_term(o[1], pv[1]));
             const float d2 = o[2] * s - pv[2] * s, d3 = o[3] * s - pv[3] * s;
             part[1] = ((double)(d2 * d2) + (double)(d3 * d3)) * 0.5;
             double c = 0;
-            for (int k = 0; k < C; ++k) c += (double)bce_term(o[5 + k], ((pc[k >> 5] >> (k & 31)) & 1u) ? 1.f : 0.f);
+            for (int k = 0; k < C; ++k) c += (double)bce_term(o[5 + k], ((pc[k >> 5] >> (k & 31)) & 1u) ? cls_hi : cls_lo);
             part[3] = c;
         }
     }
@@ -521,8 +674,8 @@ __global__ __launch_bounds__(256) void yolo_loss_final_kernel(const double* __re
 __global__ __launch_bounds__(256) void yolo_loss_bwd_kernel(const float* __restrict__ output, int masked,
                                                             const float* __restrict__ obj_mask,
                                                             const float* __restrict__ gscale_p,
-                                                            float* __restrict__ g_out, int B, int F, int A, int K,
-                                                            int C, int cw, LossPtrs w) {
+                                                            float* __restrict__ g_out, int B, int F, int A, int R,
+                                                            int C, int cw, float cls_lo, float cls_hi, LossPtrs w) {
     const int n_ch = 5 + C;
     const long long total = (long long)B * A * F * F * n_ch;
     const int per_img = A * F * F;
@@ -537,15 +690,15 @@ __global__ __launch_bounds__(256) void yolo_loss_bwd_kernel(const float* __restr
             if (obj_mask[cell] != 0.f) g = bce_grad(output[e], rec >= 0 ? 1.f : 0.f);
         } else if (rec >= 0) {
             const int b = (int)(cell / per_img);
-            const float* pv = w.pos_val + ((long long)b * K + rec) * 5;
+            const float* pv = w.pos_val + ((long long)b * R + rec) * 5;
             const float s = pv[4];
             const float o = output[e];
             if (ch < 2) g = (s * s) * bce_grad(o, pv[ch]);
             else if (ch < 4) g = ((masked ? o : o * s) - pv[ch] * s) * s;
             else {
                 const int k = ch - 5;
-                const unsigned bit = (w.pos_cls[((long long)b * K + rec) * cw + (k >> 5)] >> (k & 31)) & 1u;
-                g = bce_grad(o, bit ? 1.f : 0.f);
+                const unsigned bit = (w.pos_cls[((long long)b * R + rec) * cw + (k >> 5)] >> (k & 31)) & 1u;
+                g = bce_grad(o, bit ? cls_hi : cls_lo);
             }
         }
         g_out[e] = g * gscale;
@@ -555,7 +708,7 @@ __global__ __launch_bounds__(256) void yolo_loss_bwd_kernel(const float* __restr
 // yololoss.py:402-407: output[...,4]*=obj_mask; output[...,{0-3,5..}]*=tgt_mask; output[...,2:4]*=tgt_scale
 __global__ __launch_bounds__(256) void yolo_loss_mask_output_kernel(float* __restrict__ output,
                                                                     const float* __restrict__ obj_mask,
-                                                                    int B, int F, int A, int K, int C, LossPtrs w) {
+                                                                    int B, int F, int A, int R, int C, LossPtrs w) {
     const int n_ch = 5 + C;
     const long long total = (long long)B * A * F * F * n_ch;
     const int per_img = A * F * F;
@@ -570,7 +723,7 @@ __global__ __launch_bounds__(256) void yolo_loss_mask_output_kernel(float* __res
             v = v * (rec >= 0 ? 1.f : 0.f);
             if (ch == 2 || ch == 3) {
                 const int b = (int)(cell / per_img);
-                v = v * (rec >= 0 ? w.pos_val[((long long)b * K + rec) * 5 + 4] : 0.f);
+                v = v * (rec >= 0 ? w.pos_val[((long long)b * R + rec) * 5 + 4] : 0.f);
             }
         }
         output[e] = v;
@@ -578,20 +731,20 @@ __global__ __launch_bounds__(256) void yolo_loss_mask_output_kernel(float* __res
 }
 
 __global__ void yolo_dense_targets_kernel(float* __restrict__ target, float* __restrict__ tgt_mask,
-                                          float* __restrict__ tgt_scale, int B, int F, int A, int K, int C, int cw,
-                                          LossPtrs w) {
-    // one thread per (image, record)
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= B * K) return;
-    const int b = idx / K, rec = idx - b * K;
+                                          float* __restrict__ tgt_scale, int B, int F, int A, int R, int C, int cw,
+                                          float cls_lo, float cls_hi, LossPtrs w) {
+    // one thread per (image, record slot)
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long long)B * R) return;
+    const int b = (int)(idx / R), rec = (int)(idx - (long long)b * R);
     if (rec >= w.npos[b]) return;
     const long long cell = (long long)b * A * F * F + w.pos_cell[idx];
     const int n_ch = 5 + C;
     const float* pv = w.pos_val + (long long)idx * 5;
     float* t = target + cell * n_ch;
     t[0] = pv[0]; t[1] = pv[1]; t[2] = pv[2]; t[3] = pv[3]; t[4] = 1.f;
-    for (int k = 0; k < C; ++k)
-        if ((w.pos_cls[(long long)idx * cw + (k >> 5)] >> (k & 31)) & 1u) t[5 + k] = 1.f;
+    for (int k = 0; k < C; ++k)                                // label smoothing off: 1 and the 0 the host's memset left
+        t[5 + k] = ((w.pos_cls[(long long)idx * cw + (k >> 5)] >> (k & 31)) & 1u) ? cls_hi : cls_lo;
     float* tm = tgt_mask + cell * (4 + C);
     for (int k = 0; k < 4 + C; ++k) tm[k] = 1.f;
     tgt_scale[cell * 2] = pv[4];
@@ -600,9 +753,11 @@ __global__ void yolo_dense_targets_kernel(float* __restrict__ target, float* __r
 
 // ------------------------------------------------------------------------------------ IoU-family box loss
 // 1 - X over the positive records, X = IoU | GIoU | DIoU | CIoU of the decoded box p = pred[cell] against the record's
-// truth box (pos_box), both as (xc, yc, w, h) in grid units.  Centres come in relative to the cell origin (px - i and
-// tx - i are exact in fp32: px in [i, i + 1], i = trunc(tx)), so the corner differences do not cancel against the grid
-// offset.  Ties: a corner of p counts as the selected one of min / max only under a strict inequality, the clamp of the
+// truth box (pos_box), both as (xc, yc, w, h) in grid units.  Centres come in relative to the cell origin, so the corner
+// differences do not cancel against the grid offset.  px - i and tx - i are exact in fp32: tx is in [i, i + 1) with
+// i = trunc(tx); px is in [i - h, i + 1 + h] with h = (scale_x_y - 1) / 2 <= 0.5, where px and i are both multiples of
+// u = ulp(px) (u <= 1; i = 0 is trivial, else px >= 0.5 and u >= 2^-24) and |px - i| <= 1.5 (<= 0.5 where px < 1) is
+// below 2^24 u, so the difference is representable.  Ties: a corner of p counts as the selected one of min / max only under a strict inequality, the clamp of the
 // intersection passes a gradient only when the raw extent is > 0.  CIoU's alpha is a constant in the gradient.
 // fmaxf / fminf drop NaN operands: a NaN in p is carried to the result explicitly.
 constexpr float BOX_EPS = 1e-7f;
@@ -684,10 +839,10 @@ __device__ __forceinline__ BoxTerm box_term(int kind, float px, float py, float 
     return r;
 }
 
-// the boxes of record slot s = b * K + rec; false for an empty slot
-__device__ __forceinline__ bool box_record(const float* __restrict__ pred, int F, int A, int K, const LossPtrs& w,
+// the boxes of record slot s = b * R + rec; false for an empty slot
+__device__ __forceinline__ bool box_record(const float* __restrict__ pred, int F, int A, int R, const LossPtrs& w,
                                            long long s, long long& cell_out, float* p, float* t) {
-    const int b = (int)(s / K), rec = (int)(s - (long long)b * K);
+    const int b = (int)(s / R), rec = (int)(s - (long long)b * R);
     if (rec >= w.npos[b]) return false;
     const int per_img = A * F * F;
     const int cell = w.pos_cell[s];
@@ -704,15 +859,15 @@ __device__ __forceinline__ bool box_record(const float* __restrict__ pred, int F
 // One block: a thread adds its slots in slot order, then wave shuffles, then the 16 wave sums in order through LDS.
 constexpr int BOX_BLOCK = 1024;
 __global__ __launch_bounds__(BOX_BLOCK) void yolo_box_loss_fwd_kernel(const float* __restrict__ pred, int kind, float gain,
-                                                                      int B, int F, int A, int K, LossPtrs w,
+                                                                      int B, int F, int A, int R, LossPtrs w,
                                                                       double* __restrict__ out) {
     __shared__ double red[BOX_BLOCK / 64];
-    const long long slots = (long long)B * K;
+    const long long slots = (long long)B * R;
     double acc = 0;
     for (long long s = threadIdx.x; s < slots; s += BOX_BLOCK) {
         long long cell;
         float p[4], t[4];
-        if (box_record(pred, F, A, K, w, s, cell, p, t))
+        if (box_record(pred, F, A, R, w, s, cell, p, t))
             acc += (double)box_term<false>(kind, p[0], p[1], p[2], p[3], t[0], t[1], t[2], t[3]).loss;
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
@@ -729,18 +884,18 @@ __global__ __launch_bounds__(BOX_BLOCK) void yolo_box_loss_fwd_kernel(const floa
 // One thread per record slot: the four box channels of its cell, over what the dense backward wrote there.
 __global__ __launch_bounds__(256) void yolo_box_loss_bwd_kernel(const float* __restrict__ pred, int kind, float gain,
                                                                 const float* __restrict__ gscale_p,
-                                                                float* __restrict__ g_out, int B, int F, int A, int K,
-                                                                int n_ch, LossPtrs w) {
+                                                                float* __restrict__ g_out, int B, int F, int A, int R,
+                                                                int n_ch, float sxy, LossPtrs w) {
     const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (s >= (long long)B * K) return;
+    if (s >= (long long)B * R) return;
     long long cell;
     float p[4], t[4];
-    if (!box_record(pred, F, A, K, w, s, cell, p, t)) return;
+    if (!box_record(pred, F, A, R, w, s, cell, p, t)) return;
     const BoxTerm r = box_term<true>(kind, p[0], p[1], p[2], p[3], t[0], t[1], t[2], t[3]);
     const float gscale = *gscale_p;
     float* g = g_out + cell * n_ch;
-    g[0] = (r.g0 * gain) * gscale;
-    g[1] = (r.g1 * gain) * gscale;
+    g[0] = ((r.g0 * gain) * sxy) * gscale;                    // d pred / d output = scale_x_y on x and y (x * 1 is exact)
+    g[1] = ((r.g1 * gain) * sxy) * gscale;
     g[2] = (r.g2 * gain) * gscale;
     g[3] = (r.g3 * gain) * gscale;
 }
@@ -1437,25 +1592,67 @@ int y4_bboxes_iou_f32(const float* boxes_a, long long Na, const float* boxes_b, 
     return Y4_OK;
 }
 
-int y4_yolo_decode_train_f32(const float* logits, int ldl, float* output, float* pred,
-                             int B, int F, int A, int n_classes, const float* anchors_wh_host, void* stream) {
+int y4_yolo_decode_train_ex_f32(const float* logits, int ldl, float* output, float* pred,
+                                int B, int F, int A, int n_classes, const float* anchors_wh_host, float scale_xy,
+                                void* stream) {
     if (!logits || !output || !pred) return Y4_ERR_NULL;
     const int n_ch = 5 + n_classes;
     Anchors anc;
-    if (B <= 0 || F <= 0 || A <= 0 || n_classes <= 0 || ldl < A * n_ch || !fill_anchors(anc, anchors_wh_host, A))
+    if (B <= 0 || F <= 0 || A <= 0 || n_classes <= 0 || ldl < A * n_ch || !fill_anchors(anc, anchors_wh_host, A) ||
+        !scale_xy_ok(scale_xy))
         return Y4_ERR_SHAPE;
+    const float hxy = (scale_xy - 1.0f) * 0.5f;
     const long long npix = (long long)B * F * F;
     const int tp = decode_tp(npix);
     const long long tpi = ((long long)F * F + tp - 1) / tp;
     if (decode_tiled_ok(logits, ldl, A, n_ch, output, pred) && (long long)B * tpi < (1ll << 31)) {
-        auto kern = tp == 16 ? yolo_decode_tiled_kernel<false, 16> : yolo_decode_tiled_kernel<false, 32>;
+        const bool sc = scale_xy != 1.0f;
+        auto kern = tp == 16 ? (sc ? yolo_decode_tiled_kernel<false, 16, true> : yolo_decode_tiled_kernel<false, 16, false>)
+                             : (sc ? yolo_decode_tiled_kernel<false, 32, true> : yolo_decode_tiled_kernel<false, 32, false>);
         hipLaunchKernelGGL(kern, dim3((unsigned)(B * tpi)), dim3(256), 0, y4_stream(stream), logits,
-                           (long long)ldl, output, pred, 0ll, 0ll, 1.0f, F, A, n_ch, anc, (int)tpi);
+                           (long long)ldl, output, pred, 0ll, 0ll, 1.0f, F, A, n_ch, anc, (int)tpi, scale_xy, hxy);
         Y4_CHECK_LAUNCH();
         return Y4_OK;
     }
     hipLaunchKernelGGL(yolo_decode_kernel<false>, dim3((unsigned)(npix < 8192 ? npix : 8192)), dim3(256), 0,
-                       y4_stream(stream), logits, (long long)ldl, output, pred, 0ll, 0ll, 1.0f, B, F, A, n_ch, anc);
+                       y4_stream(stream), logits, (long long)ldl, output, pred, 0ll, 0ll, 1.0f, B, F, A, n_ch, anc,
+                       scale_xy, hxy);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+
+int y4_yolo_decode_train_f32(const float* logits, int ldl, float* output, float* pred,
+                             int B, int F, int A, int n_classes, const float* anchors_wh_host, void* stream) {
+    return y4_yolo_decode_train_ex_f32(logits, ldl, output, pred, B, F, A, n_classes, anchors_wh_host, 1.0f, stream);
+}
+
+int y4_yolo_decode_eval_ex_f32(const float* logits, int ldl, float* out, long long n_total, long long box_off,
+                               int B, int F, int A, int n_classes, const float* anchors_wh_host,
+                               float stride, float scale_xy, void* stream) {
+    if (!logits || !out) return Y4_ERR_NULL;
+    const int n_ch = 5 + n_classes;
+    Anchors anc;
+    if (B <= 0 || F <= 0 || A <= 0 || n_classes <= 0 || ldl < A * n_ch || !fill_anchors(anc, anchors_wh_host, A) ||
+        !scale_xy_ok(scale_xy))
+        return Y4_ERR_SHAPE;
+    if (box_off < 0 || box_off + (long long)A * F * F > n_total) return Y4_ERR_SHAPE;
+    const float hxy = (scale_xy - 1.0f) * 0.5f;
+    const long long npix = (long long)B * F * F;
+    const int tp = decode_tp(npix);
+    const long long tpi = ((long long)F * F + tp - 1) / tp;
+    if (decode_tiled_ok(logits, ldl, A, n_ch, out, nullptr) && (long long)B * tpi < (1ll << 31)) {
+        const bool sc = scale_xy != 1.0f;
+        auto kern = tp == 16 ? (sc ? yolo_decode_tiled_kernel<true, 16, true> : yolo_decode_tiled_kernel<true, 16, false>)
+                             : (sc ? yolo_decode_tiled_kernel<true, 32, true> : yolo_decode_tiled_kernel<true, 32, false>);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(B * tpi)), dim3(256), 0, y4_stream(stream), logits,
+                           (long long)ldl, out, (float*)nullptr, n_total, box_off, stride, F, A, n_ch, anc, (int)tpi,
+                           scale_xy, hxy);
+        Y4_CHECK_LAUNCH();
+        return Y4_OK;
+    }
+    hipLaunchKernelGGL(yolo_decode_kernel<true>, dim3((unsigned)(npix < 8192 ? npix : 8192)), dim3(256), 0,
+                       y4_stream(stream), logits, (long long)ldl, out, (float*)nullptr, n_total, box_off, stride, B, F,
+                       A, n_ch, anc, scale_xy, hxy);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
@@ -1463,25 +1660,22 @@ int y4_yolo_decode_train_f32(const float* logits, int ldl, float* output, float*
 int y4_yolo_decode_eval_f32(const float* logits, int ldl, float* out, long long n_total, long long box_off,
                             int B, int F, int A, int n_classes, const float* anchors_wh_host,
                             float stride, void* stream) {
-    if (!logits || !out) return Y4_ERR_NULL;
+    return y4_yolo_decode_eval_ex_f32(logits, ldl, out, n_total, box_off, B, F, A, n_classes, anchors_wh_host, stride,
+                                      1.0f, stream);
+}
+
+int y4_yolo_decode_bwd_ex_f32(const float* logits, int ldl, const float* g_output, const float* g_pred,
+                              float* g_logits, int B, int F, int A, int n_classes,
+                              const float* anchors_wh_host, float scale_xy, void* stream) {
+    if (!logits || !g_logits) return Y4_ERR_NULL;
     const int n_ch = 5 + n_classes;
     Anchors anc;
-    if (B <= 0 || F <= 0 || A <= 0 || n_classes <= 0 || ldl < A * n_ch || !fill_anchors(anc, anchors_wh_host, A))
+    if (B <= 0 || F <= 0 || A <= 0 || n_classes <= 0 || ldl < A * n_ch || !fill_anchors(anc, anchors_wh_host, A) ||
+        !scale_xy_ok(scale_xy))
         return Y4_ERR_SHAPE;
-    if (box_off < 0 || box_off + (long long)A * F * F > n_total) return Y4_ERR_SHAPE;
     const long long npix = (long long)B * F * F;
-    const int tp = decode_tp(npix);
-    const long long tpi = ((long long)F * F + tp - 1) / tp;
-    if (decode_tiled_ok(logits, ldl, A, n_ch, out, nullptr) && (long long)B * tpi < (1ll << 31)) {
-        auto kern = tp == 16 ? yolo_decode_tiled_kernel<true, 16> : yolo_decode_tiled_kernel<true, 32>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(B * tpi)), dim3(256), 0, y4_stream(stream), logits,
-                           (long long)ldl, out, (float*)nullptr, n_total, box_off, stride, F, A, n_ch, anc, (int)tpi);
-        Y4_CHECK_LAUNCH();
-        return Y4_OK;
-    }
-    hipLaunchKernelGGL(yolo_decode_kernel<true>, dim3((unsigned)(npix < 8192 ? npix : 8192)), dim3(256), 0,
-                       y4_stream(stream), logits, (long long)ldl, out, (float*)nullptr, n_total, box_off, stride, B, F,
-                       A, n_ch, anc);
+    hipLaunchKernelGGL(yolo_decode_bwd_kernel, dim3((unsigned)(npix < 8192 ? npix : 8192)), dim3(256), 0,
+                       y4_stream(stream), logits, (long long)ldl, g_output, g_pred, g_logits, B, F, A, n_ch, anc, scale_xy);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
@@ -1489,21 +1683,71 @@ int y4_yolo_decode_eval_f32(const float* logits, int ldl, float* out, long long 
 int y4_yolo_decode_bwd_f32(const float* logits, int ldl, const float* g_output, const float* g_pred,
                            float* g_logits, int B, int F, int A, int n_classes,
                            const float* anchors_wh_host, void* stream) {
-    if (!logits || !g_logits) return Y4_ERR_NULL;
-    const int n_ch = 5 + n_classes;
-    Anchors anc;
-    if (B <= 0 || F <= 0 || A <= 0 || n_classes <= 0 || ldl < A * n_ch || !fill_anchors(anc, anchors_wh_host, A))
-        return Y4_ERR_SHAPE;
-    const long long npix = (long long)B * F * F;
-    hipLaunchKernelGGL(yolo_decode_bwd_kernel, dim3((unsigned)(npix < 8192 ? npix : 8192)), dim3(256), 0,
-                       y4_stream(stream), logits, (long long)ldl, g_output, g_pred, g_logits, B, F, A, n_ch, anc);
-    Y4_CHECK_LAUNCH();
-    return Y4_OK;
+    return y4_yolo_decode_bwd_ex_f32(logits, ldl, g_output, g_pred, g_logits, B, F, A, n_classes, anchors_wh_host, 1.0f,
+                                     stream);
+}
+
+// the shape conditions every loss entry shares; B * R * 5 and the record slots stay inside int
+static bool loss_dims_ok(int B, int F, int A, int K, int n_classes) {
+    return B > 0 && F > 0 && A > 0 && K > 0 && n_classes > 0 && (long long)B * K * A < (1ll << 31);
+}
+
+size_t y4_yolo_loss_workspace_ex(int B, int F, int A, int K, int n_classes, float iou_thresh) {
+    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_ok(iou_thresh, 0.f)) return 0;
+    return loss_ws(B, F, A, K, n_classes, loss_rec_cap(K, A, iou_thresh)).total;
 }
 
 size_t y4_yolo_loss_workspace(int B, int F, int A, int K, int n_classes) {
     if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0) return 0;
-    return loss_ws(B, F, A, K, n_classes).total;
+    return loss_ws(B, F, A, K, n_classes, K).total;
+}
+
+int y4_yolo_loss_fwd_ex_f32(const float* output, const float* pred, const float* labels, int K,
+                            int B, int F, int A, int n_classes, float stride, float ignore_thresh,
+                            const float* all_anchors_host, int n_all_anchors, const int* anch_mask_host,
+                            float iou_thresh, float label_smooth, float* obj_mask, double* loss_parts,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    if (!output || !pred || !labels || !obj_mask || !loss_parts || !workspace || !anch_mask_host) return Y4_ERR_NULL;
+    if (B <= 0 || F <= 0 || A != 3 || K <= 0 || n_classes <= 0 || (long long)A * F * F >= (1ll << 31)) return Y4_ERR_SHAPE;
+    if (!loss_opts_ok(iou_thresh, label_smooth) || (long long)B * K * A >= (1ll << 31)) return Y4_ERR_SHAPE;
+    const bool multi = iou_thresh < 1.f;
+    Anchors all, masked;
+    if (!fill_anchors(all, all_anchors_host, n_all_anchors)) return Y4_ERR_SHAPE;
+    float mwh[6];
+    for (int a = 0; a < 3; ++a) {
+        const int id = anch_mask_host[a];
+        if (id < 0 || id >= n_all_anchors) return Y4_ERR_SHAPE;
+        if (multi && id % 3 != a) return Y4_ERR_SHAPE;         // the arg-max's slot (best % 3) must be its place in the mask
+        mwh[2 * a] = all_anchors_host[2 * id]; mwh[2 * a + 1] = all_anchors_host[2 * id + 1];
+    }
+    fill_anchors(masked, mwh, 3);
+    const int R = loss_rec_cap(K, A, iou_thresh);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
+    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
+    const LossPtrs w = loss_ptrs(workspace, l);
+    const float cls_lo = 0.5f * label_smooth, cls_hi = 1.0f - cls_lo;      // Darknet's rule; 0 and 1 without smoothing
+    hipStream_t st = y4_stream(stream);
+    if (hipMemsetAsync(w.pos_index, 0xff, (size_t)B * A * F * F * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
+    const int m0 = anch_mask_host[0], m1 = anch_mask_host[1], m2 = anch_mask_host[2];
+    if (K <= 64) {
+        if (multi)
+            hipLaunchKernelGGL(yolo_assign_wave_multi_kernel, dim3(B), dim3(64), 0, st, labels, K, R, B, F, A, n_classes,
+                               l.cw, stride, all, n_all_anchors, m0, m1, m2, masked, iou_thresh, w);
+        else
+            hipLaunchKernelGGL(yolo_assign_wave_kernel, dim3(B), dim3(64), 0, st, labels, K, B, F, A, n_classes, l.cw,
+                               stride, all, n_all_anchors, m0, m1, m2, masked, w);
+    } else {
+        auto kern = multi ? yolo_assign_kernel<true> : yolo_assign_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((B + 63) / 64), dim3(64), 0, st, labels, K, R, B, F, A, n_classes, l.cw, stride, all,
+                           n_all_anchors, m0, m1, m2, masked, iou_thresh, w);
+    }
+    Y4_CHECK_LAUNCH();
+    hipLaunchKernelGGL(yolo_loss_dense_kernel, dim3(l.nblocks), dim3(LOSS_BLOCK), 0, st, output, pred, B, F, A, K, R,
+                       n_classes, l.cw, ignore_thresh, cls_lo, cls_hi, obj_mask, w);
+    Y4_CHECK_LAUNCH();
+    hipLaunchKernelGGL(yolo_loss_final_kernel, dim3(1), dim3(256), 0, st, w.partials, l.nblocks, loss_parts);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
 }
 
 int y4_yolo_loss_fwd_f32(const float* output, const float* pred, const float* labels, int K,
@@ -1511,34 +1755,26 @@ int y4_yolo_loss_fwd_f32(const float* output, const float* pred, const float* la
                          const float* all_anchors_host, int n_all_anchors, const int* anch_mask_host,
                          float* obj_mask, double* loss_parts,
                          void* workspace, size_t workspace_bytes, void* stream) {
-    if (!output || !pred || !labels || !obj_mask || !loss_parts || !workspace || !anch_mask_host) return Y4_ERR_NULL;
-    if (B <= 0 || F <= 0 || A != 3 || K <= 0 || n_classes <= 0 || (long long)A * F * F >= (1ll << 31)) return Y4_ERR_SHAPE;
-    Anchors all, masked;
-    if (!fill_anchors(all, all_anchors_host, n_all_anchors)) return Y4_ERR_SHAPE;
-    float mwh[6];
-    for (int a = 0; a < 3; ++a) {
-        const int id = anch_mask_host[a];
-        if (id < 0 || id >= n_all_anchors) return Y4_ERR_SHAPE;
-        mwh[2 * a] = all_anchors_host[2 * id]; mwh[2 * a + 1] = all_anchors_host[2 * id + 1];
-    }
-    fill_anchors(masked, mwh, 3);
-    const LossWs l = loss_ws(B, F, A, K, n_classes);
+    return y4_yolo_loss_fwd_ex_f32(output, pred, labels, K, B, F, A, n_classes, stride, ignore_thresh, all_anchors_host,
+                                   n_all_anchors, anch_mask_host, 1.0f, 0.0f, obj_mask, loss_parts, workspace,
+                                   workspace_bytes, stream);
+}
+
+int y4_yolo_loss_bwd_ex_f32(const float* output, int output_is_masked, const float* obj_mask,
+                            const float* gscale, float* g_output,
+                            int B, int F, int A, int K, int n_classes, float iou_thresh, float label_smooth,
+                            const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!output || !obj_mask || !g_output || !workspace || !gscale) return Y4_ERR_NULL;
+    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_ok(iou_thresh, label_smooth)) return Y4_ERR_SHAPE;
+    const int R = loss_rec_cap(K, A, iou_thresh);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
     if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
     const LossPtrs w = loss_ptrs(workspace, l);
-    hipStream_t st = y4_stream(stream);
-    if (hipMemsetAsync(w.pos_index, 0xff, (size_t)B * A * F * F * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
-    if (K <= 64) {
-        hipLaunchKernelGGL(yolo_assign_wave_kernel, dim3(B), dim3(64), 0, st, labels, K, B, F, A, n_classes, l.cw,
-                           stride, all, n_all_anchors, anch_mask_host[0], anch_mask_host[1], anch_mask_host[2], masked, w);
-    } else {
-        hipLaunchKernelGGL(yolo_assign_kernel, dim3((B + 63) / 64), dim3(64), 0, st, labels, K, B, F, A, n_classes, l.cw,
-                           stride, all, n_all_anchors, anch_mask_host[0], anch_mask_host[1], anch_mask_host[2], masked, w);
-    }
-    Y4_CHECK_LAUNCH();
-    hipLaunchKernelGGL(yolo_loss_dense_kernel, dim3(l.nblocks), dim3(LOSS_BLOCK), 0, st, output, pred, B, F, A, K,
-                       n_classes, l.cw, ignore_thresh, obj_mask, w);
-    Y4_CHECK_LAUNCH();
-    hipLaunchKernelGGL(yolo_loss_final_kernel, dim3(1), dim3(256), 0, st, w.partials, l.nblocks, loss_parts);
+    const float cls_lo = 0.5f * label_smooth, cls_hi = 1.0f - cls_lo;
+    const long long total = (long long)B * A * F * F * (5 + n_classes);
+    hipLaunchKernelGGL(yolo_loss_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, y4_stream(stream), output,
+                       output_is_masked, obj_mask,
+                       gscale, g_output, B, F, A, R, n_classes, l.cw, cls_lo, cls_hi, w);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
@@ -1547,29 +1783,49 @@ int y4_yolo_loss_bwd_f32(const float* output, int output_is_masked, const float*
                          const float* gscale, float* g_output,
                          int B, int F, int A, int K, int n_classes,
                          const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!output || !obj_mask || !g_output || !workspace || !gscale) return Y4_ERR_NULL;
-    if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0) return Y4_ERR_SHAPE;
-    const LossWs l = loss_ws(B, F, A, K, n_classes);
+    return y4_yolo_loss_bwd_ex_f32(output, output_is_masked, obj_mask, gscale, g_output, B, F, A, K, n_classes, 1.0f, 0.0f,
+                                   workspace, workspace_bytes, stream);
+}
+
+int y4_yolo_loss_mask_output_ex_f32(float* output, const float* obj_mask, int B, int F, int A, int K,
+                                    int n_classes, float iou_thresh, const void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    if (!output || !obj_mask || !workspace) return Y4_ERR_NULL;
+    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_ok(iou_thresh, 0.f)) return Y4_ERR_SHAPE;
+    const int R = loss_rec_cap(K, A, iou_thresh);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
     if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
     const LossPtrs w = loss_ptrs(workspace, l);
     const long long total = (long long)B * A * F * F * (5 + n_classes);
-    hipLaunchKernelGGL(yolo_loss_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, y4_stream(stream), output,
-                       output_is_masked, obj_mask,
-                       gscale, g_output, B, F, A, K, n_classes, l.cw, w);
+    hipLaunchKernelGGL(yolo_loss_mask_output_kernel, dim3(grid_for(total)), dim3(256), 0, y4_stream(stream), output,
+                       obj_mask, B, F, A, R, n_classes, w);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
 
 int y4_yolo_loss_mask_output_f32(float* output, const float* obj_mask, int B, int F, int A, int K,
                                  int n_classes, const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!output || !obj_mask || !workspace) return Y4_ERR_NULL;
-    if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0) return Y4_ERR_SHAPE;
-    const LossWs l = loss_ws(B, F, A, K, n_classes);
+    return y4_yolo_loss_mask_output_ex_f32(output, obj_mask, B, F, A, K, n_classes, 1.0f, workspace, workspace_bytes, stream);
+}
+
+int y4_yolo_loss_dense_targets_ex_f32(float* target, float* tgt_mask, float* tgt_scale,
+                                      int B, int F, int A, int K, int n_classes, float iou_thresh, float label_smooth,
+                                      const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!target || !tgt_mask || !tgt_scale || !workspace) return Y4_ERR_NULL;
+    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_ok(iou_thresh, label_smooth)) return Y4_ERR_SHAPE;
+    const int R = loss_rec_cap(K, A, iou_thresh);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
     if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
     const LossPtrs w = loss_ptrs(workspace, l);
-    const long long total = (long long)B * A * F * F * (5 + n_classes);
-    hipLaunchKernelGGL(yolo_loss_mask_output_kernel, dim3(grid_for(total)), dim3(256), 0, y4_stream(stream), output,
-                       obj_mask, B, F, A, K, n_classes, w);
+    const float cls_lo = 0.5f * label_smooth, cls_hi = 1.0f - cls_lo;
+    hipStream_t st = y4_stream(stream);
+    const size_t cells = (size_t)B * A * F * F;
+    if (hipMemsetAsync(target, 0, cells * (5 + n_classes) * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
+    if (hipMemsetAsync(tgt_mask, 0, cells * (4 + n_classes) * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
+    if (hipMemsetAsync(tgt_scale, 0, cells * 2 * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
+    const long long slots = (long long)B * R;
+    hipLaunchKernelGGL(yolo_dense_targets_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, target, tgt_mask,
+                       tgt_scale, B, F, A, R, n_classes, l.cw, cls_lo, cls_hi, w);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
@@ -1577,34 +1833,47 @@ int y4_yolo_loss_mask_output_f32(float* output, const float* obj_mask, int B, in
 int y4_yolo_loss_dense_targets_f32(float* target, float* tgt_mask, float* tgt_scale,
                                    int B, int F, int A, int K, int n_classes,
                                    const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!target || !tgt_mask || !tgt_scale || !workspace) return Y4_ERR_NULL;
-    if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0) return Y4_ERR_SHAPE;
-    const LossWs l = loss_ws(B, F, A, K, n_classes);
-    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
-    const LossPtrs w = loss_ptrs(workspace, l);
-    hipStream_t st = y4_stream(stream);
-    const size_t cells = (size_t)B * A * F * F;
-    if (hipMemsetAsync(target, 0, cells * (5 + n_classes) * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
-    if (hipMemsetAsync(tgt_mask, 0, cells * (4 + n_classes) * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
-    if (hipMemsetAsync(tgt_scale, 0, cells * 2 * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
-    hipLaunchKernelGGL(yolo_dense_targets_kernel, dim3((B * K + 255) / 256), dim3(256), 0, st, target, tgt_mask,
-                       tgt_scale, B, F, A, K, n_classes, l.cw, w);
-    Y4_CHECK_LAUNCH();
-    return Y4_OK;
+    return y4_yolo_loss_dense_targets_ex_f32(target, tgt_mask, tgt_scale, B, F, A, K, n_classes, 1.0f, 0.0f, workspace,
+                                             workspace_bytes, stream);
 }
 
 static bool box_kind_ok(int kind) { return kind >= Y4_BOX_IOU && kind <= Y4_BOX_CIOU; }
 
-int y4_yolo_box_loss_fwd_f32(const float* pred, int box_kind, float gain, int B, int F, int A, int K, int n_classes,
-                             double* loss_parts, const void* workspace, size_t workspace_bytes, void* stream) {
+int y4_yolo_box_loss_fwd_ex_f32(const float* pred, int box_kind, float gain, int B, int F, int A, int K, int n_classes,
+                                float iou_thresh, double* loss_parts, const void* workspace, size_t workspace_bytes,
+                                void* stream) {
     if (!pred || !loss_parts || !workspace) return Y4_ERR_NULL;
-    if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0 || (long long)A * F * F >= (1ll << 31) ||
-        !box_kind_ok(box_kind)) return Y4_ERR_SHAPE;
-    const LossWs l = loss_ws(B, F, A, K, n_classes);
+    if (!loss_dims_ok(B, F, A, K, n_classes) || (long long)A * F * F >= (1ll << 31) || !box_kind_ok(box_kind) ||
+        !loss_opts_ok(iou_thresh, 0.f)) return Y4_ERR_SHAPE;
+    const int R = loss_rec_cap(K, A, iou_thresh);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
     if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
     const LossPtrs w = loss_ptrs(workspace, l);
     hipLaunchKernelGGL(yolo_box_loss_fwd_kernel, dim3(1), dim3(BOX_BLOCK), 0, y4_stream(stream), pred, box_kind, gain,
-                       B, F, A, K, w, loss_parts);
+                       B, F, A, R, w, loss_parts);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+
+int y4_yolo_box_loss_fwd_f32(const float* pred, int box_kind, float gain, int B, int F, int A, int K, int n_classes,
+                             double* loss_parts, const void* workspace, size_t workspace_bytes, void* stream) {
+    return y4_yolo_box_loss_fwd_ex_f32(pred, box_kind, gain, B, F, A, K, n_classes, 1.0f, loss_parts, workspace,
+                                       workspace_bytes, stream);
+}
+
+int y4_yolo_box_loss_bwd_ex_f32(const float* pred, int box_kind, float gain, const float* gscale, float* g_output,
+                                int B, int F, int A, int K, int n_classes, float iou_thresh, float scale_xy,
+                                const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!pred || !gscale || !g_output || !workspace) return Y4_ERR_NULL;
+    if (!loss_dims_ok(B, F, A, K, n_classes) || (long long)A * F * F >= (1ll << 31) || !box_kind_ok(box_kind) ||
+        !loss_opts_ok(iou_thresh, 0.f) || !scale_xy_ok(scale_xy)) return Y4_ERR_SHAPE;
+    const int R = loss_rec_cap(K, A, iou_thresh);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
+    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
+    const LossPtrs w = loss_ptrs(workspace, l);
+    const long long slots = (long long)B * R;
+    hipLaunchKernelGGL(yolo_box_loss_bwd_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, y4_stream(stream),
+                       pred, box_kind, gain, gscale, g_output, B, F, A, R, 5 + n_classes, scale_xy, w);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
@@ -1612,18 +1881,8 @@ int y4_yolo_box_loss_fwd_f32(const float* pred, int box_kind, float gain, int B,
 int y4_yolo_box_loss_bwd_f32(const float* pred, int box_kind, float gain, const float* gscale, float* g_output,
                              int B, int F, int A, int K, int n_classes,
                              const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!pred || !gscale || !g_output || !workspace) return Y4_ERR_NULL;
-    if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0 || (long long)A * F * F >= (1ll << 31) ||
-        !box_kind_ok(box_kind)) return Y4_ERR_SHAPE;
-    const LossWs l = loss_ws(B, F, A, K, n_classes);
-    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
-    const LossPtrs w = loss_ptrs(workspace, l);
-    const long long slots = (long long)B * K;
-    if ((slots + 255) / 256 >= (1ll << 31)) return Y4_ERR_SHAPE;
-    hipLaunchKernelGGL(yolo_box_loss_bwd_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, y4_stream(stream),
-                       pred, box_kind, gain, gscale, g_output, B, F, A, K, 5 + n_classes, w);
-    Y4_CHECK_LAUNCH();
-    return Y4_OK;
+    return y4_yolo_box_loss_bwd_ex_f32(pred, box_kind, gain, gscale, g_output, B, F, A, K, n_classes, 1.0f, 1.0f, workspace,
+                                       workspace_bytes, stream);
 }
 
 int y4_post_count_ex_f32(float* prediction, int B, long long N, int n_classes, float conf_thre,

@@ -1588,12 +1588,22 @@ class Slot:
 
 
 # ------------------------------------------------------------------ YOLO head
+def check_scale_xy(s):
+    """scale_x_y as a float; ValueError outside [1, 2] (NaN included), before anything touches a GPU."""
+    s = float(s)
+    if not 1.0 <= s <= 2.0:
+        raise ValueError(f'scale_x_y must be in [1, 2], got {s!r}')
+    return s
+
+
 class YoloDecodeTrainFn(torch.autograd.Function):
-    """YOLOLayer.forward train branch, yolo/model/yololayer.py:88-145."""
+    """YOLOLayer.forward train branch, yolo/model/yololayer.py:88-145.  scale_xy: the YOLOv4 grid-sensitivity factor
+    (pred centre = sigmoid * s - (s - 1) / 2 + cell); 1.0 is the reference's decode, bit for bit."""
 
     @staticmethod
-    def forward(ctx, logits, anchors_wh, n_classes):
+    def forward(ctx, logits, anchors_wh, n_classes, scale_xy=1.0):
         L = lib()
+        scale_xy = check_scale_xy(scale_xy)
         _require_gpu(logits, 'YOLOLayer input')
         B, ch, F, F2 = logits.shape
         if F != F2:
@@ -1604,10 +1614,11 @@ class YoloDecodeTrainFn(torch.autograd.Function):
         output = torch.empty((B, A, F, F, n_ch), device=logits.device, dtype=torch.float32)
         pred = torch.empty((B, A, F, F, 4), device=logits.device, dtype=torch.float32)
         anc = float_array([v for wh in anchors_wh for v in wh])
-        check(L.y4_yolo_decode_train_f32(_ptr(logits), ldl, _ptr(output), _ptr(pred), B, F, A, n_classes, anc,
-                                         _stream()), 'yolo_decode_train')
+        check(L.y4_yolo_decode_train_ex_f32(_ptr(logits), ldl, _ptr(output), _ptr(pred), B, F, A, n_classes, anc,
+                                            scale_xy, _stream()), 'yolo_decode_train')
         ctx.save_for_backward(logits)
         ctx.meta = (B, F, A, n_classes, anchors_wh, ldl)
+        ctx.scale_xy = scale_xy
         return output, pred
 
     @staticmethod
@@ -1629,16 +1640,17 @@ class YoloDecodeTrainFn(torch.autograd.Function):
             lg = empty_nhwc(B, A * n_ch, F, F, logits.device, pad_to=32)
             lg.copy_(logits)
             ldl2 = cpad
-        check(L.y4_yolo_decode_bwd_f32(_ptr(lg), ldl2, _ptr(g_output), _ptr(g_pred), _ptr(gl), B, F, A, n_classes,
-                                       anc, _stream()), 'yolo_decode_bwd')
-        return gl, None, None
+        check(L.y4_yolo_decode_bwd_ex_f32(_ptr(lg), ldl2, _ptr(g_output), _ptr(g_pred), _ptr(gl), B, F, A, n_classes,
+                                          anc, ctx.scale_xy, _stream()), 'yolo_decode_bwd')
+        return gl, None, None, None
 
 
-def yolo_decode_eval(logits, anchors_wh, n_classes, stride, out=None, n_total=None, box_off=0):
+def yolo_decode_eval(logits, anchors_wh, n_classes, stride, out=None, n_total=None, box_off=0, scale_xy=1.0):
     """YOLOLayer.forward eval branch, yolo/model/yololayer.py:146-166; optionally writes straight
     into rows [box_off, box_off + A*F*F) of a shared [B, n_total, 5+C] buffer (the torch.cat of
-    yolo/model/yolov4.py:324 without a copy)."""
+    yolo/model/yolov4.py:324 without a copy).  scale_xy as in YoloDecodeTrainFn."""
     L = lib()
+    scale_xy = check_scale_xy(scale_xy)
     _require_gpu(logits, 'YOLOLayer input')
     B, ch, F, _ = logits.shape
     n_ch = 5 + n_classes
@@ -1649,8 +1661,8 @@ def yolo_decode_eval(logits, anchors_wh, n_classes, stride, out=None, n_total=No
         out = torch.empty((B, n_total, n_ch), device=logits.device, dtype=torch.float32)
         box_off = 0
     anc = float_array([v for wh in anchors_wh for v in wh])
-    check(L.y4_yolo_decode_eval_f32(_ptr(logits), ldl, _ptr(out), n_total, box_off, B, F, A, n_classes, anc,
-                                    float(stride), _stream()), 'yolo_decode_eval')
+    check(L.y4_yolo_decode_eval_ex_f32(_ptr(logits), ldl, _ptr(out), n_total, box_off, B, F, A, n_classes, anc,
+                                       float(stride), scale_xy, _stream()), 'yolo_decode_eval')
     return out
 
 
@@ -1665,16 +1677,30 @@ def box_loss_kind(name):
         raise ValueError(f'unknown box_loss {name!r}: expected one of {sorted(BOX_LOSS_KINDS)}') from None
 
 
+def check_loss_options(iou_thresh, label_smooth):
+    """(iou_thresh, label_smooth) as floats; ValueError outside (0, 1] / [0, 1), before anything touches a GPU."""
+    iou_thresh, label_smooth = float(iou_thresh), float(label_smooth)
+    if not 0.0 < iou_thresh <= 1.0:
+        raise ValueError(f'iou_thresh must be in (0, 1] (1 = one positive anchor per label), got {iou_thresh!r}')
+    if not 0.0 <= label_smooth < 1.0:
+        raise ValueError(f'label_smooth must be in [0, 1), got {label_smooth!r}')
+    return iou_thresh, label_smooth
+
+
 class YoloLossLayerFn(torch.autograd.Function):
     """YOLOLoss.build_target + loss terms for one layer, yolo/model/yololoss.py:118-371,385-432.  With
     cfg['box_loss'] in {'iou', 'giou', 'diou', 'ciou'} the xy / wh terms are replaced by cfg['box_gain'] * sum(1 - X)
-    over the positive records (parts[0]; parts[1] = 0): two more launches on the same workspace."""
+    over the positive records (parts[0]; parts[1] = 0): two more launches on the same workspace.  Optional
+    cfg['iou_thresh'] (several positive anchors per label), cfg['label_smooth'] (class targets) and cfg['scale_xy'] (the
+    layer's decode factor, for the box gradient): include/yolov4_amd.h, "YOLOv4 head options of the loss"."""
 
     @staticmethod
     def forward(ctx, output, pred, labels, cfg):
         L = lib()
         box_kind = box_loss_kind(cfg.get('box_loss', 'mse'))
         box_gain = float(cfg.get('box_gain', 1.0))
+        iou_thresh, label_smooth = check_loss_options(cfg.get('iou_thresh', 1.0), cfg.get('label_smooth', 0.0))
+        scale_xy = check_scale_xy(cfg.get('scale_xy', 1.0))
         _require_gpu(output, 'YOLOLoss output')
         B, A, F, _, n_ch = output.shape
         C = n_ch - 5
@@ -1683,45 +1709,51 @@ class YoloLossLayerFn(torch.autograd.Function):
             raise Y4Error('YOLOLoss: `output` must be contiguous [B,A,F,F,5+C]')
         pred = pred.detach().contiguous()
         labels = labels.detach().to(device=output.device, dtype=torch.float32).contiguous()
-        nbytes = L.y4_yolo_loss_workspace(B, F, A, K, C)
+        nbytes = L.y4_yolo_loss_workspace_ex(B, F, A, K, C, iou_thresh)
         ws = _ws(nbytes, output.device)
         obj_mask = torch.empty((B, A, F, F), device=output.device, dtype=torch.float32)
         parts = torch.empty(4, device=output.device, dtype=torch.float64)
         anchors = float_array([v for wh in cfg['all_anchors'] for v in wh])
         amask = int_array(cfg['anch_mask'])
-        check(L.y4_yolo_loss_fwd_f32(_ptr(output), _ptr(pred), _ptr(labels), K, B, F, A, C, float(cfg['stride']),
-                                     float(cfg['ignore_thresh']), anchors, len(cfg['all_anchors']), amask,
-                                     _ptr(obj_mask), _ptr(parts), _ptr(ws), nbytes, _stream()), 'yolo_loss_fwd')
+        check(L.y4_yolo_loss_fwd_ex_f32(_ptr(output), _ptr(pred), _ptr(labels), K, B, F, A, C, float(cfg['stride']),
+                                        float(cfg['ignore_thresh']), anchors, len(cfg['all_anchors']), amask,
+                                        iou_thresh, label_smooth, _ptr(obj_mask), _ptr(parts), _ptr(ws), nbytes,
+                                        _stream()), 'yolo_loss_fwd')
         if box_kind:
-            check(L.y4_yolo_box_loss_fwd_f32(_ptr(pred), box_kind, box_gain, B, F, A, K, C, _ptr(parts), _ptr(ws),
-                                             nbytes, _stream()), 'yolo_box_loss_fwd')
+            check(L.y4_yolo_box_loss_fwd_ex_f32(_ptr(pred), box_kind, box_gain, B, F, A, K, C, iou_thresh, _ptr(parts),
+                                                _ptr(ws), nbytes, _stream()), 'yolo_box_loss_fwd')
         ctx.box = (box_kind, box_gain, pred if box_kind else None)      # the backward reads the box from pred
         ctx.meta = (B, F, A, K, C, nbytes)
+        ctx.opts = (iou_thresh, label_smooth, scale_xy)
         ctx.ws = ws
         ctx.obj_mask = obj_mask
         ctx.output = output          # later mutated in place exactly like the reference does
         ctx.mutate = cfg.get('mutate_output', True)
-        cfg['last'] = dict(obj_mask=obj_mask, parts=parts, ws=ws, nbytes=nbytes, dims=(B, F, A, K, C))
+        cfg['last'] = dict(obj_mask=obj_mask, parts=parts, ws=ws, nbytes=nbytes, dims=(B, F, A, K, C),
+                           iou_thresh=iou_thresh, label_smooth=label_smooth,
+                           rec_cap=K * A if iou_thresh < 1.0 else K)    # record slots per image in ws
         loss = parts.sum().to(torch.float32)
         if ctx.mutate:
             # side effect of yololoss.py:402-407 on outputs[*]['output']; done through the raw pointer,
             # the backward kernel is told that the w/h channels already carry the scale factor
-            check(L.y4_yolo_loss_mask_output_f32(_ptr(output), _ptr(obj_mask), B, F, A, K, C, _ptr(ws), nbytes,
-                                                 _stream()), 'yolo_loss_mask_output')
+            check(L.y4_yolo_loss_mask_output_ex_f32(_ptr(output), _ptr(obj_mask), B, F, A, K, C, iou_thresh, _ptr(ws),
+                                                    nbytes, _stream()), 'yolo_loss_mask_output')
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
         L = lib()
         B, F, A, K, C, nbytes = ctx.meta
+        iou_thresh, label_smooth, scale_xy = ctx.opts
         g = torch.empty_like(ctx.output)
         gs = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        check(L.y4_yolo_loss_bwd_f32(_ptr(ctx.output), 1 if ctx.mutate else 0, _ptr(ctx.obj_mask), _ptr(gs), _ptr(g),
-                                     B, F, A, K, C, _ptr(ctx.ws), nbytes, _stream()), 'yolo_loss_bwd')
+        check(L.y4_yolo_loss_bwd_ex_f32(_ptr(ctx.output), 1 if ctx.mutate else 0, _ptr(ctx.obj_mask), _ptr(gs), _ptr(g),
+                                        B, F, A, K, C, iou_thresh, label_smooth, _ptr(ctx.ws), nbytes, _stream()),
+              'yolo_loss_bwd')
         box_kind, box_gain, pred = ctx.box
         if box_kind:
-            check(L.y4_yolo_box_loss_bwd_f32(_ptr(pred), box_kind, box_gain, _ptr(gs), _ptr(g), B, F, A, K, C,
-                                             _ptr(ctx.ws), nbytes, _stream()), 'yolo_box_loss_bwd')
+            check(L.y4_yolo_box_loss_bwd_ex_f32(_ptr(pred), box_kind, box_gain, _ptr(gs), _ptr(g), B, F, A, K, C,
+                                                iou_thresh, scale_xy, _ptr(ctx.ws), nbytes, _stream()), 'yolo_box_loss_bwd')
         return g, None, None, None
 
 
@@ -1733,8 +1765,9 @@ def yolo_loss_dense_targets(last):
     target = torch.empty((B, A, F, F, 5 + C), device=dev, dtype=torch.float32)
     tgt_mask = torch.empty((B, A, F, F, 4 + C), device=dev, dtype=torch.float32)
     tgt_scale = torch.empty((B, A, F, F, 2), device=dev, dtype=torch.float32)
-    check(L.y4_yolo_loss_dense_targets_f32(_ptr(target), _ptr(tgt_mask), _ptr(tgt_scale), B, F, A, K, C,
-                                           _ptr(last['ws']), last['nbytes'], _stream()), 'yolo_loss_dense_targets')
+    check(L.y4_yolo_loss_dense_targets_ex_f32(_ptr(target), _ptr(tgt_mask), _ptr(tgt_scale), B, F, A, K, C,
+                                              last.get('iou_thresh', 1.0), last.get('label_smooth', 0.0),
+                                              _ptr(last['ws']), last['nbytes'], _stream()), 'yolo_loss_dense_targets')
     return target, tgt_mask, tgt_scale
 
 

@@ -17,4 +17,6 @@ def build_model(args: Namespace, cfg: Dict, device=None):
 def build_criterion(cfg: Dict, device=None):
     crit = cfg['CRITERION']
     return YOLOLoss(cfg['MODEL'], ignore_thresh=float(crit['IGNORE_THRESH']), device=device,
-                    box_loss=crit.get('BOX_LOSS', 'mse'), box_gain=float(crit.get('BOX_LOSS_GAIN', 1.0))).to(device)
+                    box_loss=crit.get('BOX_LOSS', 'mse'), box_gain=float(crit.get('BOX_LOSS_GAIN', 1.0)),
+                    iou_thresh=float(crit.get('IOU_THRESH', 1.0)),
+                    label_smooth=float(crit.get('LABEL_SMOOTH', 0.0))).to(device)

@@ -8,6 +8,17 @@ from torch import nn
 from ... import ops
 
 
+def layer_scale_xy(cfg, layer_no):
+    """The layer's YOLOv4 grid-sensitivity factor from the optional cfg['SCALE_X_Y'] (one number, or one per layer;
+    Darknet: 1.2 / 1.1 / 1.05 for strides 8 / 16 / 32); 1.0 when the key is absent.  ValueError outside [1, 2]."""
+    v = cfg.get('SCALE_X_Y', 1.0)
+    if isinstance(v, (list, tuple)):
+        if len(v) != 3:
+            raise ValueError(f"SCALE_X_Y must be one number or one per layer (3), got {v!r}")
+        v = v[layer_no]
+    return ops.check_scale_xy(v)
+
+
 class YOLOLayer(nn.Module):
     strides = [8, 16, 32]
 
@@ -21,6 +32,7 @@ class YOLOLayer(nn.Module):
         self.all_anchors_grid = [(w / self.stride, h / self.stride) for w, h in self.anchors]
         self.masked_anchors = torch.from_numpy(np.array([self.all_anchors_grid[i] for i in self.anchor_mask]))
         self.n_classes = cfg['N_CLASSES']
+        self.scale_xy = layer_scale_xy(cfg, layer_no)
         self.device = device
 
     def _anchors_f32(self):
@@ -29,10 +41,11 @@ class YOLOLayer(nn.Module):
 
     def forward(self, output):
         if self.training:
-            out, pred = ops.YoloDecodeTrainFn.apply(output, self._anchors_f32(), self.n_classes)
+            out, pred = ops.YoloDecodeTrainFn.apply(output, self._anchors_f32(), self.n_classes, self.scale_xy)
             return {'layer_no': self.layer_no, 'output': out, 'pred': pred}
-        return ops.yolo_decode_eval(output, self._anchors_f32(), self.n_classes, self.stride)
+        return ops.yolo_decode_eval(output, self._anchors_f32(), self.n_classes, self.stride, scale_xy=self.scale_xy)
 
     def decode_into(self, logits, out, n_total, box_off):
         """eval decode straight into rows [box_off, ...) of the concatenated [B, n_total, 5+C] buffer"""
-        return ops.yolo_decode_eval(logits, self._anchors_f32(), self.n_classes, self.stride, out, n_total, box_off)
+        return ops.yolo_decode_eval(logits, self._anchors_f32(), self.n_classes, self.stride, out, n_total, box_off,
+                                    scale_xy=self.scale_xy)

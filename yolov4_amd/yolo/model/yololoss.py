@@ -3,7 +3,10 @@
 YOLOv3-style weighted-BCE(xy) + MSE(wh)/2 + BCE(obj) + BCE(cls), summed over batch and
 the 3 layers (no CIoU / focal anywhere in the reference).  Opt-in beyond the
 reference: box_loss = 'iou' | 'giou' | 'diou' | 'ciou' replaces the xy / wh terms by
-box_gain * sum(1 - X) over the positive cells ("IoU-family box losses")."""
+box_gain * sum(1 - X) over the positive cells (DESIGN.md, "IoU-family box losses");
+iou_thresh < 1 makes every anchor whose shape IoU with a label exceeds it positive (Darknet's
+iou_thresh, 0.213 in yolov4.cfg), label_smooth smooths the class BCE targets, and the model
+cfg's SCALE_X_Y reaches the box-loss gradient."""
 from typing import Dict
 
 import numpy as np
@@ -11,6 +14,7 @@ import torch
 from torch import nn
 
 from ... import ops
+from .yololayer import layer_scale_xy
 
 
 def bboxes_iou(bboxes_a, bboxes_b, xyxy=True):
@@ -22,9 +26,15 @@ def bboxes_iou(bboxes_a, bboxes_b, xyxy=True):
 class YOLOLoss(nn.Module):
     strides = [8, 16, 32]
 
-    def __init__(self, cfg: Dict, ignore_thresh=0.7, device=None, mutate_outputs=True, box_loss='mse', box_gain=1.0):
+    def __init__(self, cfg: Dict, ignore_thresh=0.7, device=None, mutate_outputs=True, box_loss='mse', box_gain=1.0,
+                 iou_thresh=1.0, label_smooth=0.0):
         super().__init__()
         ops.box_loss_kind(box_loss)                 # ValueError for an unknown name, before anything touches a GPU
+        self.iou_thresh, self.label_smooth = ops.check_loss_options(iou_thresh, label_smooth)
+        self.scale_xy = [layer_scale_xy(cfg, l) for l in range(3)]
+        if box_loss == 'mse' and any(s != 1.0 for s in self.scale_xy):
+            # the xy BCE target is defined against the unscaled sigmoid; Darknet does not combine the two either
+            raise ValueError("SCALE_X_Y != 1 needs an IoU-family box_loss ('iou', 'giou', 'diou', 'ciou'), not 'mse'")
         self.box_loss = box_loss
         self.box_gain = float(box_gain)
         self.cfg = cfg
@@ -42,10 +52,12 @@ class YOLOLoss(nn.Module):
         grid = [(float(np.float32(w / st)), float(np.float32(h / st))) for w, h in self.anchors]
         return {'stride': st, 'ignore_thresh': float(np.float32(self.ignore_thresh)), 'all_anchors': grid,
                 'anch_mask': list(self.cfg['ANCHOR_MASK'][layer_no]), 'mutate_output': self.mutate_outputs,
-                'box_loss': self.box_loss, 'box_gain': self.box_gain}
+                'box_loss': self.box_loss, 'box_gain': self.box_gain, 'iou_thresh': self.iou_thresh,
+                'label_smooth': self.label_smooth, 'scale_xy': self.scale_xy[layer_no]}
 
     def build_target(self, output, pred, layer_no, labels):
-        """Dense (target, obj_mask, tgt_mask, tgt_scale) as yololoss.py:118-371 returns them."""
+        """Dense (target, obj_mask, tgt_mask, tgt_scale) as yololoss.py:118-371 returns them; with the options, every
+        positive anchor's cell is filled and target[..., 5:] holds the smoothed class targets there."""
         cfg = self._layer_cfg(layer_no)
         cfg['mutate_output'] = False
         cfg['box_loss'] = 'mse'                     # the dense targets do not depend on the box loss
