@@ -364,6 +364,35 @@ int y4_maxpool_s1_fwd_f32(const float* x, int ldx, float* y, int ldy, signed cha
                           int B, int H, int W, int C, int ksize, void* stream);
 int y4_maxpool_s1_bwd_f32(const float* dy, int lddy, const signed char* idx, float* dx, int lddx,
                           int accumulate, int B, int H, int W, int C, int ksize, void* stream);
+/* nn.MaxPool2d(2, 2) (YOLOv4-tiny; csrc/tiny.hip): y[B, H/2, W/2, C], floor -- an odd last row / column is not read.
+ * Arguments as y4_maxpool_s1_*: NHWC with pixel pitches (x may be a concat buffer or a channel slice), C % 4 == 0,
+ * pitches % 4 == 0, 16-byte aligned bases.  idx (int8 per output element, dense [B*Ho*Wo][C]; NULL in inference): the code
+ * 2*dy + dx of the selected element; selection is aten's (row-major scan, v > best || isnan(v): the first maximum wins a
+ * tie, the last NaN keeps the code).  Backward writes EVERY element of dx exactly once (dy where the code points, 0
+ * elsewhere and in a dropped odd row / column): no pre-zeroing, no accumulation.  H < 2 or W < 2: no output element;
+ * forward returns Y4_OK without a launch, backward (dy, idx may then be NULL) fills dx with zeros. */
+int y4_maxpool2x2_s2_fwd_f32(const float* x, int ldx, float* y, int ldy, signed char* idx, int B, int H, int W, int C,
+                             void* stream);
+int y4_maxpool2x2_s2_bwd_f32(const float* dy, int lddy, const signed char* idx, float* dx, int lddx, int B, int H, int W, int C,
+                             void* stream);
+/* Gradient fan-in of Darknet's half-channel route (route groups=2 group_id=1: a tensor read whole and as its upper half):
+ * dx[M, C] = g_full[M, C] + [0 | g_hi[M, C/2]]; g_full or g_hi (not both) may be NULL and stands for zeros.  C % 8 == 0,
+ * pitches % 4 == 0, 16-byte aligned bases; dx may alias g_full.  One launch, every element of dx written once. */
+int y4_fork_half_bwd_f32(const float* g_full, int ldf, const float* g_hi, int ldh, float* dx, int ldx, long long M, int C,
+                         void* stream);
+/* Stem conv 3 -> Cout, 3x3, STRIDE 2, pad 1 (YOLOv4-tiny's first layer; csrc/tiny.hip), Cout % 4 == 0, Cout <= 64.
+ * x by element strides as y4_conv2d_stem_fwd_f32, w KRSC [Cout][3][3][3], y / dy NHWC [B, Ho, Wo, Cout] with a pitch
+ * (% 4, 16-byte aligned base), Ho = (H - 1) / 2 + 1.  Forward: one fp32 fma chain per output over the in-bounds taps in
+ * (r, q, c) order, then scale / shift / act as y4_conv2d_generic_fwd_f32 -- the same bits as that kernel.
+ * wgrad: dw[n][r][q][c] = sum over output pixels of dy x; per-block partial slabs in `workspace`
+ * (y4_conv2d_stem_s2_wgrad_workspace bytes, 16-byte aligned), folded in fp64 in a fixed order (deterministic). */
+int y4_conv2d_stem_s2_fwd_f32(const float* x, long long sxb, long long sxc, long long sxh, long long sxw, const float* w,
+                              float* y, int ldy, int B, int H, int W, int Cout, const float* scale, const float* shift, int act,
+                              void* stream);
+size_t y4_conv2d_stem_s2_wgrad_workspace(int B, int H, int W, int Cout);
+int y4_conv2d_stem_s2_wgrad_f32(const float* x, long long sxb, long long sxc, long long sxh, long long sxw, const float* dy,
+                                int lddy, float* dw, int B, int H, int W, int Cout, void* workspace, size_t workspace_bytes,
+                                void* stream);
 /* nearest x2 upsample, yolov4.py:77-90, and its adjoint (2x2 block sum). */
 int y4_upsample2x_fwd_f32(const float* x, int ldx, float* y, int ldy, int B, int H, int W, int C, void* stream);
 int y4_upsample2x_bwd_f32(const float* dy, int lddy, float* dx, int lddx, int B, int H, int W, int C, void* stream);

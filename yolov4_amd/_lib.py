@@ -78,6 +78,12 @@ PROTOTYPES = {
     'y4_add_f32': (I, [P, I, P, I, P, I, L, I, P]),
     'y4_maxpool_s1_fwd_f32': (I, [P, I, P, I, P, I, I, I, I, I, P]),
     'y4_maxpool_s1_bwd_f32': (I, [P, I, P, P, I, I, I, I, I, I, I, P]),
+    'y4_maxpool2x2_s2_fwd_f32': (I, [P, I, P, I, P, I, I, I, I, P]),
+    'y4_maxpool2x2_s2_bwd_f32': (I, [P, I, P, P, I, I, I, I, I, P]),
+    'y4_fork_half_bwd_f32': (I, [P, I, P, I, P, I, L, I, P]),
+    'y4_conv2d_stem_s2_fwd_f32': (I, [P, L, L, L, L, P, P, I, I, I, I, I, P, P, I, P]),
+    'y4_conv2d_stem_s2_wgrad_workspace': (Z, [I, I, I, I]),
+    'y4_conv2d_stem_s2_wgrad_f32': (I, [P, L, L, L, L, P, I, P, I, I, I, I, P, Z, P]),
     'y4_upsample2x_fwd_f32': (I, [P, I, P, I, I, I, I, I, P]),
     'y4_upsample2x_bwd_f32': (I, [P, I, P, I, I, I, I, I, P]),
     'y4_yolo_decode_train_f32': (I, [P, I, P, P, I, I, I, I, P, P]),

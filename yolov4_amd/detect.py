@@ -138,7 +138,7 @@ def load_cfg(path):
 def build_parser():
     ap = argparse.ArgumentParser(description='YOLOv4 detection on JPEG files')
     ap.add_argument('--cfg', required=True)
-    ap.add_argument('--ckpt', default=None, help='a checkpoint in the reference format')
+    ap.add_argument('--ckpt', default=None, help='a checkpoint in the reference format, or (YOLOv4Tiny) a Darknet .weights file')
     ap.add_argument('--source', required=True, help='a .jpg file or a directory of them')
     ap.add_argument('--dest', default='./runs/detect/')
     ap.add_argument('--names', default=None, help='text file with one class name per line')
@@ -173,7 +173,7 @@ def nms_options_from_args(args, cfg):
 
 
 def main(argv=None):
-    from .yolo.model.yolov4 import YOLOv4
+    from .yolo.model.build import build_model
     from .yolo.util.checkpoint import load_checkpoint
     args = build_parser().parse_args(argv)
     cfg = load_cfg(args.cfg)
@@ -182,8 +182,11 @@ def main(argv=None):
     if not paths:
         raise SystemExit('no .jpg files in ' + args.source)
     device = torch.device('cuda')
-    model = YOLOv4(cfg['MODEL'], device=device).to(device)
-    if args.ckpt:
+    model = build_model(None, cfg, device=device)       # MODEL.TYPE: YOLOv4 or YOLOv4Tiny
+    if args.ckpt and hasattr(model, 'darknet_convs') and not args.ckpt.endswith(('.pth.tar', '.pth', '.pt')):
+        from .yolo.util.darknet_weights import load_darknet_weights
+        load_darknet_weights(model, args.ckpt)          # a Darknet .weights file (yolov4-tiny.weights)
+    elif args.ckpt:
         load_checkpoint(model, args.ckpt)
     save_dir = increment_path(os.path.join(args.dest, 'exp'))
     os.makedirs(save_dir)

@@ -232,6 +232,15 @@ def fast_conv_shape(Cin, k, s):
     return k in (1, 3) and s in (1, 2) and (Cin % 32 == 0 or (Cin == 3 and k == 3 and s == 1))
 
 
+# YOLOv4-tiny's stem (3 -> Cout, 3x3, stride 2) on the kernels of csrc/tiny.hip; Y4_TINY_STEM=0 keeps the direct kernels of
+# csrc/conv_generic.hip (the A/B switch and fallback; forward results are the same bits either way)
+_TINY_STEM = {'on': os.environ.get('Y4_TINY_STEM', '1') != '0'}
+
+
+def tiny_stem_shape(Cin, Cout, k, s):
+    return _TINY_STEM['on'] and Cin == 3 and k == 3 and s == 2 and Cout % 4 == 0 and 0 < Cout <= 64
+
+
 def planes_stride2_ok(k, s, H, W):
     """The 3x3 stride-2 layers run on the plane kernels (forward; wgrad with x read at 4 p - 2 w) on even maps, f16x2 only."""
     # (bf16 operands: only in the hybrid mode, whose register-staged stride-2 dgrad is the f16x2 one; mode 2 keeps stride 2 off planes)
@@ -282,6 +291,11 @@ def conv_fwd_raw(x, w, k, s, scale=None, shift=None, act='linear', residual=None
         out = empty_nhwc(B, Cout, Ho, Wo, x.device, pad_to=out_pad)
     ldy = nhwc_pitch(out)
     w = krsc(w)
+    if tiny_stem_shape(Cin, Cout, k, s) and residual is None and ldy % 4 == 0 and out.data_ptr() % 16 == 0:
+        sb, sc, sh, sw = x.stride()
+        check(L.y4_conv2d_stem_s2_fwd_f32(_ptr(x), sb, sc, sh, sw, _ptr(w), _ptr(out), ldy, B, H, W, Cout,
+                                          _ptr(scale), _ptr(shift), ACT_IDS[act], _stream()), 'conv2d_stem_s2_fwd')
+        return out
     if not fast_conv_shape(Cin, k, s) or (Cin == 3 and (Cout > 32 or residual is not None)):
         if k % 2 == 0:
             raise Y4Error('even kernel sizes are not supported (pad = (k - 1) // 2 would not keep the map size)')
@@ -645,6 +659,14 @@ def conv_wgrad_raw(x, dy, w_shape, k, s, out=None, x_amax=None, dy_amax=None):
         WGRAD_STATS['temporary'] += 1
         dw = torch.empty(w_shape, device=dy.device, dtype=torch.float32).contiguous(memory_format=CL)
         dw = krsc(dw)
+    if tiny_stem_shape(Cin, Cout, k, s):
+        dy, lddy = as_nhwc(dy)
+        nbytes = L.y4_conv2d_stem_s2_wgrad_workspace(B, H, W, Cout)
+        ws = _ws(nbytes, dy.device)
+        sb, sc, sh, sw = x.stride()
+        check(L.y4_conv2d_stem_s2_wgrad_f32(_ptr(x), sb, sc, sh, sw, _ptr(dy), lddy, _ptr(dw), B, H, W, Cout,
+                                            _ptr(ws), nbytes, _stream()), 'conv2d_stem_s2_wgrad')
+        return dw
     if k not in (1, 3) or s not in (1, 2) or (Cin % 4 and Cin != 3) or (Cin == 3 and (k != 3 or s != 1 or Cout > 32)):
         xs, ldx = as_nhwc(x, need_vec4=False)
         dys, lddy = as_nhwc(dy, need_vec4=False)
@@ -1461,6 +1483,85 @@ class MaxPoolS1Fn(torch.autograd.Function):
         check(L.y4_maxpool_s1_bwd_f32(_ptr(g), ldg, _ptr(ctx.idx), _ptr(dx), nhwc_pitch(dx), 0, B, H, W, C, ctx.ks,
                                       _stream()), 'maxpool_bwd')
         return dx, None
+
+
+class MaxPool2x2Fn(torch.autograd.Function):
+    """nn.MaxPool2d(2, 2) (YOLOv4-tiny, csrc/tiny.hip).  The input may be a concat buffer or a channel slice."""
+
+    @staticmethod
+    def forward(ctx, x, out=None):
+        L = lib()
+        _require_gpu(x, 'maxpool2x2 input')
+        B, C, H, W = x.shape
+        x, ldx = as_nhwc(x)
+        out = out.t if (out is not None and _slot_ok(out.t, (B, C, H // 2, W // 2))) else empty_nhwc(B, C, H // 2, W // 2, x.device)
+        # the codes serve backward alone: inference allocates none
+        idx = torch.empty((B, H // 2, W // 2, C), dtype=torch.int8, device=x.device) if ctx.needs_input_grad[0] else None
+        check(L.y4_maxpool2x2_s2_fwd_f32(_ptr(x), ldx, _ptr(out), nhwc_pitch(out), _ptr(idx), B, H, W, C, _stream()), 'maxpool2x2')
+        ctx.idx, ctx.shape = idx, (B, C, H, W)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        L = lib()
+        B, C, H, W = ctx.shape
+        g, ldg = as_nhwc(g)
+        dx = empty_nhwc(B, C, H, W, g.device)                # written whole by the kernel: no zero fill
+        check(L.y4_maxpool2x2_s2_bwd_f32(_ptr(g), ldg, _ptr(ctx.idx), _ptr(dx), nhwc_pitch(dx), B, H, W, C, _stream()),
+              'maxpool2x2_bwd')
+        return dx, None
+
+
+def maxpool2x2(x, out=None):
+    """nn.MaxPool2d(2, 2); max|out| <= max|x| (pooling selects elements): the result carries x's operand-maximum cell, as
+    spp_pool_cat's does.  out: optional destination (a CatBuffer slot); x's maximum then folds into that buffer's shared cell."""
+    y = MaxPool2x2Fn.apply(x, Slot(out) if out is not None else None)
+    cell, shared = amax_of(x), amax_of(out)
+    if shared is not None and y.data_ptr() == out.data_ptr():
+        if cell is None:
+            cell = amax_raw(x)
+        amax_merge(shared, cell)
+        return tag_amax(y, shared)
+    return tag_amax(y, cell)
+
+
+class ForkHalfFn(torch.autograd.Function):
+    """Darknet's `route groups=2 group_id=1`: x read whole and as its upper channel half (a view, no copy).  Backward is the
+    fan-in of the two gradients in at most one launch (y4_fork_half_bwd_f32) into a FRESH buffer: g_full usually is a slice
+    view of somebody else's gradient buffer (CatFn.backward hands out views), which is never written here."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.set_materialize_grads(False)
+        return x.view_as(x), x[:, x.shape[1] // 2:]
+
+    @staticmethod
+    def backward(ctx, g_full, g_hi):
+        if g_hi is None:
+            return g_full                                # (None, or the whole-tensor gradient as it is: no launch)
+        B, Ch, H, W = g_hi.shape
+        C = 2 * Ch
+        g_hi, ldh = as_nhwc(g_hi)
+        ldf = 0
+        if g_full is not None:
+            g_full, ldf = as_nhwc(g_full)
+        dx = empty_nhwc(B, C, H, W, g_hi.device)
+        check(lib().y4_fork_half_bwd_f32(_ptr(g_full), ldf, _ptr(g_hi), ldh, _ptr(dx), nhwc_pitch(dx), B * H * W, C, _stream()),
+              'fork_half_bwd')
+        return dx
+
+
+def fork_half(x):
+    """(x_full, x_hi): x for its whole-tensor reader and the view x[:, C // 2:] for the reader of its upper half (C % 8 == 0).
+    Both carry x's operand-maximum cell (an upper bound for the half)."""
+    if x.dim() != 4 or x.shape[1] % 8:
+        raise Y4Error('fork_half: a 4-D tensor with a channel count that is a multiple of 8')
+    if not (torch.is_grad_enabled() and x.requires_grad):
+        return x, tag_amax(x[:, x.shape[1] // 2:], amax_of(x))
+    _require_gpu(x, 'fork_half input')
+    a, b = ForkHalfFn.apply(x)
+    cell = amax_of(x)
+    return tag_amax(a, cell), tag_amax(b, cell)
 
 
 class Upsample2xFn(torch.autograd.Function):

@@ -4,13 +4,24 @@ from argparse import Namespace
 from typing import Dict
 
 from .yolov4 import YOLOv4
+from .yolov4_tiny import YOLOv4Tiny
 from .yololoss import YOLOLoss
+
+MODELS = {'YOLOv4': YOLOv4, 'YOLOv4Tiny': YOLOv4Tiny}
+
+
+def model_class(model_cfg: Dict):
+    """The network class cfg['MODEL']['TYPE'] names; ValueError for an unknown one."""
+    kind = model_cfg.get('TYPE')
+    if kind not in MODELS:
+        raise ValueError(f"unknown MODEL.TYPE {kind!r}: one of {sorted(MODELS)}")
+    return MODELS[kind]
 
 
 def build_model(args: Namespace, cfg: Dict, device=None):
     # activations and filters are NHWC / KRSC on this path whatever args.channels_last says
     # (the flag only selected a memory format in the reference, build.py:20-26)
-    model = YOLOv4(cfg['MODEL'], device=device)
+    model = model_class(cfg['MODEL'])(cfg['MODEL'], device=device)
     return model.to(device=device)
 
 

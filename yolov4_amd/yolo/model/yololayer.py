@@ -8,13 +8,27 @@ from torch import nn
 from ... import ops
 
 
+def n_layers(cfg):
+    """Number of detection layers: one per anchor mask (3 for YOLOv4, 2 for YOLOv4-tiny)."""
+    return len(cfg['ANCHOR_MASK']) if 'ANCHOR_MASK' in cfg else 3
+
+
+def layer_strides(cfg, default):
+    """cfg['STRIDES'] (one per layer; YOLOv4-tiny: [16, 32]), else the class default [8, 16, 32]."""
+    st = [int(v) for v in cfg.get('STRIDES', default)]
+    if len(st) < n_layers(cfg):
+        raise ValueError(f"STRIDES must name one stride per layer ({n_layers(cfg)}), got {st!r}")
+    return st
+
+
 def layer_scale_xy(cfg, layer_no):
     """The layer's YOLOv4 grid-sensitivity factor from the optional cfg['SCALE_X_Y'] (one number, or one per layer;
     Darknet: 1.2 / 1.1 / 1.05 for strides 8 / 16 / 32); 1.0 when the key is absent.  ValueError outside [1, 2]."""
     v = cfg.get('SCALE_X_Y', 1.0)
     if isinstance(v, (list, tuple)):
-        if len(v) != 3:
-            raise ValueError(f"SCALE_X_Y must be one number or one per layer (3), got {v!r}")
+        n = n_layers(cfg)
+        if len(v) != n:
+            raise ValueError(f"SCALE_X_Y must be one number or one per layer ({n}), got {v!r}")
         v = v[layer_no]
     return ops.check_scale_xy(v)
 
@@ -24,7 +38,7 @@ class YOLOLayer(nn.Module):
 
     def __init__(self, cfg, layer_no, device=None):
         super().__init__()
-        self.stride = self.strides[layer_no]
+        self.stride = layer_strides(cfg, self.strides)[layer_no]
         self.layer_no = layer_no
         self.anchors = cfg['ANCHORS']
         self.anchor_mask = cfg['ANCHOR_MASK'][layer_no]

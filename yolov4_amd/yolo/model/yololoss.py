@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from ... import ops
-from .yololayer import layer_scale_xy
+from .yololayer import layer_scale_xy, layer_strides, n_layers
 
 
 def bboxes_iou(bboxes_a, bboxes_b, xyxy=True):
@@ -31,7 +31,7 @@ class YOLOLoss(nn.Module):
         super().__init__()
         ops.box_loss_kind(box_loss)                 # ValueError for an unknown name, before anything touches a GPU
         self.iou_thresh, self.label_smooth = ops.check_loss_options(iou_thresh, label_smooth)
-        self.scale_xy = [layer_scale_xy(cfg, l) for l in range(3)]
+        self.scale_xy = [layer_scale_xy(cfg, l) for l in range(n_layers(cfg))]
         if box_loss == 'mse' and any(s != 1.0 for s in self.scale_xy):
             # the xy BCE target is defined against the unscaled sigmoid; Darknet does not combine the two either
             raise ValueError("SCALE_X_Y != 1 needs an IoU-family box_loss ('iou', 'giou', 'diou', 'ciou'), not 'mse'")
@@ -44,10 +44,10 @@ class YOLOLoss(nn.Module):
         self.n_classes = cfg['N_CLASSES']
         # yololoss.py:402-407 multiplies the masks into outputs[*]['output'] in place; kept by default
         self.mutate_outputs = mutate_outputs
-        self.last = [None, None, None]
+        self.last = [None] * n_layers(cfg)
 
     def _layer_cfg(self, layer_no):
-        st = self.strides[layer_no]
+        st = layer_strides(self.cfg, self.strides)[layer_no]
         # anchors / stride in float64, used as fp32 (yololoss.py:155-167)
         grid = [(float(np.float32(w / st)), float(np.float32(h / st))) for w, h in self.anchors]
         return {'stride': st, 'ignore_thresh': float(np.float32(self.ignore_thresh)), 'all_anchors': grid,
