@@ -987,6 +987,59 @@ typedef struct y4_draw_job {
  * below 1, a pitch below 3 * width, a negative count, half < 0, scale < 1 or a text range outside [0, text_bytes] Y4_ERR_SHAPE. */
 int y4_draw_boxes_u8(const y4_draw_job* jobs_dev, const y4_draw_job* jobs_host, int n_images, void* stream);
 
+/* ---------------------------------------------------------------- ImageNet input pipeline (what torchvision and Pillow do for
+ * the reference's darknet/main_amp.py:205-332): per sample crop -> Pillow's antialiased bilinear resample of the crop to
+ * res_h x res_w -> an S x S window of that image -> horizontal flip -> CutMix paste -> (float(u8) - mean[c]) / std[c] into
+ * fp32 planes, ONE gather launch per batch behind one small launch that builds the coefficient tables.  No crop image, no
+ * resized image and no uint8 batch exists anywhere.  One record per output sample (96 bytes): */
+typedef struct y4_rcrop_job {
+    const void* src;                /* device, uint8 [src_h, src_w, 3] (what y4_jpeg_decode_u8 writes) */
+    long long src_pitch;            /* bytes per source row, >= 3 * src_w; any alignment */
+    int src_h, src_w;
+    int swap_rb;                    /* 0: output channel c is memory channel c; 1: memory channel 2 - c (BGR source -> RGB) */
+    int crop_x, crop_y, crop_w, crop_h;   /* the crop, inside the source; taps never leave it */
+    int res_w, res_h;               /* size the crop is resampled to */
+    int win_x, win_y;               /* origin of the S x S window in the resampled image */
+    int flip;                       /* 1: output column ox shows window column S - 1 - ox */
+    int paste_from;                 /* -1, or the sample of this batch whose pixels fill the rectangle below */
+    int paste_x0, paste_y0, paste_x1, paste_y1;   /* output coordinates, x0 <= x < x1, y0 <= y < y1; may be empty */
+    long long ws_offset;            /* bytes, multiple of 16: this job's tables in the workspace (4 bytes of padding before) */
+} y4_rcrop_job;
+/* The arithmetic is Pillow's Image.crop(box).resize((res_w, res_h), Image.BILINEAR) for 8-bit RGB, bit for bit.  Per axis,
+ * with `in` the crop's size and `out` the resampled size, in IEEE double without fused multiply-add:
+ *   scale = (double)in / out; fs = max(scale, 1.0); support = fs; ksize = (int)ceil(support) * 2 + 1; ss = 1.0 / fs;
+ *   for resampled index xx: center = (xx + 0.5) * scale; xmin = max((int)(center - support + 0.5), 0);
+ *   n = min((int)(center + support + 0.5), in) - xmin (both casts truncate);
+ *   w[x] = max(0, 1 - |(x + xmin - center + 0.5) * ss|) for x < n, summed in index order into ww, each divided by ww when
+ *   ww != 0; k[x] = (int)(0.5 + w[x] * 4194304.0).
+ * The horizontal pass runs first over the crop's rows: clip((2^21 + sum px * k) >> 22, 0, 255) in int32, kept as 8 bits; the
+ * vertical pass applies the same formula to those values.  An axis whose size does not change has taps {2^22, 0}: the
+ * identity, as Pillow's skipped pass.  The last step is the correctly rounded fp32 (float(u8) - mean[c]) / std[c] with c the
+ * OUTPUT channel (no reciprocal).
+ * CutMix: a pixel (oy, ox) with paste_from >= 0 inside the rectangle is computed from job paste_from's record and tables at
+ * the same (oy, ox) -- with that job's flip, without that job's own paste -- so the result is plain[paste_from][:, oy, ox],
+ * plain being the batch without pastes.
+ *
+ * Workspace: per job, at ws_offset, two int32 tables, the x axis first: bounds[S][2] = (xmin, n) of window index i (resampled
+ * index win + i), then k[S][ksize] with the taps beyond n zero; ksize by the formula above from (crop_w, res_w) or (crop_h,
+ * res_h).  A job takes 4 * (S * (2 + ksize_x) + S * (2 + ksize_y)) bytes rounded up to 16; y4_rcrop_workspace is the sum over
+ * the jobs in order (0 for a NULL table, n < 1, S outside [1, 65535] or a crop / resampled size below 1 or a crop above 65535).
+ * y4_rcrop_coeffs_i32 fills the tables only; y4_rcrop_u8_f32 fills them and gathers (two launches).  Device pointers, no
+ * allocation, no synchronisation; the table is passed twice like the augmentation tables (jobs_dev is what the kernels read,
+ * jobs_host the same bytes in host memory).  dst is addressed as b * dst_sb + c * dst_sc + y * dst_sh + x * dst_sw (elements):
+ * every element of the [n, 3, S, S] destination is overwritten, nothing else is written.
+ * Errors before any launch: NULL pointer (a job's src included) Y4_ERR_NULL; n outside [1, 65535], S outside [1, 65535], a
+ * source side outside [1, 65535], a pitch below 3 * src_w, an empty crop or one outside the source, res_w or res_h outside
+ * [1, 65535], a window outside the resampled image, paste_from outside [-1, n), with paste_from >= 0 a rectangle that is not
+ * 0 <= x0 <= x1 <= S and 0 <= y0 <= y1 <= S, a negative or misaligned ws_offset, a std[c] that is zero or a mean / std that
+ * is not finite Y4_ERR_SHAPE; ws_offset + the job's bytes beyond ws_bytes Y4_ERR_WORKSPACE. */
+size_t y4_rcrop_workspace(const y4_rcrop_job* jobs_host, int n, int S);
+int y4_rcrop_coeffs_i32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs_host, int n, int S, void* workspace,
+                        size_t ws_bytes, void* stream);
+int y4_rcrop_u8_f32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs_host, int n, int S, const float* mean3_host,
+                    const float* std3_host, float* dst, long long dst_sb, long long dst_sc, long long dst_sh, long long dst_sw,
+                    void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

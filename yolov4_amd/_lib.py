@@ -154,6 +154,9 @@ PROTOTYPES = {
     'y4_jpeg_encode_bound': (Z, [P]),
     'y4_jpeg_encode_host': (I, [P, P, P, P, Z, P]),
     'y4_draw_boxes_u8': (I, [P, P, I, P]),
+    'y4_rcrop_workspace': (Z, [P, I, I]),
+    'y4_rcrop_coeffs_i32': (I, [P, P, I, I, P, Z, P]),
+    'y4_rcrop_u8_f32': (I, [P, P, I, I, P, P, P, L, L, L, L, P, Z, P]),
 }
 
 ERR_FORMAT, ERR_UNSUPPORTED = 6, 7
@@ -213,6 +216,14 @@ class DrawJob(ctypes.Structure):
     _fields_ = [('image', c_void_p), ('pitch', c_longlong), ('width', c_int), ('height', c_int), ('boxes', c_void_p),
                 ('boxes_host', c_void_p), ('text', c_void_p), ('glyphs', c_void_p), ('n_boxes', c_int), ('text_bytes', c_int),
                 ('n_glyphs', c_int), ('reserved', c_int)]
+
+
+class RcropJob(ctypes.Structure):
+    """y4_rcrop_job (96 bytes)"""
+    _fields_ = [('src', c_void_p), ('src_pitch', c_longlong), ('src_h', c_int), ('src_w', c_int), ('swap_rb', c_int),
+                ('crop_x', c_int), ('crop_y', c_int), ('crop_w', c_int), ('crop_h', c_int), ('res_w', c_int), ('res_h', c_int),
+                ('win_x', c_int), ('win_y', c_int), ('flip', c_int), ('paste_from', c_int), ('paste_x0', c_int),
+                ('paste_y0', c_int), ('paste_x1', c_int), ('paste_y1', c_int), ('ws_offset', c_longlong)]
 
 
 _lib = None

@@ -1,5 +1,7 @@
 # -*- coding: utf-8 -*-
 """Loss and metric of the classifier's training script (darknet/main_amp.py:184, 549-562) on the library's kernels."""
+from collections import namedtuple
+
 from torch import nn
 
 from .. import ops
@@ -26,6 +28,18 @@ class CrossEntropyLoss(nn.Module):
 
     def forward(self, input, target):
         return ops.CESmoothFn.apply(input, target, self.label_smoothing)
+
+
+# The target of a CutMix batch (darknet/data.py): a the samples' own classes, b their partners', lam the own share.
+MixedTarget = namedtuple('MixedTarget', 'a b lam')
+
+
+def mixed_loss(criterion, output, target):
+    """criterion(output, target) for a tensor target; lam * criterion(output, a) + (1 - lam) * criterion(output, b) for a
+    MixedTarget (the CutMix paper's loss)."""
+    if isinstance(target, MixedTarget):
+        return criterion(output, target.a) * target.lam + criterion(output, target.b) * (1.0 - target.lam)
+    return criterion(output, target)
 
 
 def accuracy(output, target, topk=(1,)):

@@ -1,11 +1,13 @@
 # -*- coding: utf-8 -*-
 """Training helpers of the classifier with the reference's call order (darknet/main_amp.py:335-490, 518-546), without apex
-and without the CUDA prefetcher: loaders are plain iterables of (input, target) device batches."""
+and without the CUDA prefetcher: loaders are plain iterables of (input, target) device batches (darknet/data.py makes them
+from image files).  A target is an int64 tensor, or on a CutMix batch a MixedTarget, whose loss is `mixed_loss` and whose
+accuracy is scored against the samples' own classes."""
 import time
 
 import torch
 
-from .loss import accuracy
+from .loss import MixedTarget, accuracy, mixed_loss
 
 
 class AverageMeter(object):
@@ -49,7 +51,7 @@ def adjust_learning_rate(optimizer, base_lr, epoch, step, len_epoch):
 def train_step(model, criterion, optimizer, input, target):
     """One iteration of main_amp.py:358-376: forward, loss, zero_grad, backward, step.  Returns (output, loss)."""
     output = model(input)
-    loss = criterion(output, target)
+    loss = mixed_loss(criterion, output, target)
     optimizer.zero_grad()
     loss.backward()
     optimizer.step()
@@ -66,7 +68,8 @@ def train(train_loader, model, criterion, optimizer, epoch, base_lr, print_freq=
         lr = adjust_learning_rate(optimizer, base_lr, epoch, i, n)
         output, loss = train_step(model, criterion, optimizer, input, target)
         if i % print_freq == 0:
-            prec1, prec5 = accuracy(output.data, target, topk=(1, 5))
+            own = target.a if isinstance(target, MixedTarget) else target
+            prec1, prec5 = accuracy(output.data, own, topk=(1, 5))
             losses.update(float(loss.detach()), input.size(0))
             top1.update(float(prec1), input.size(0))
             top5.update(float(prec5), input.size(0))
