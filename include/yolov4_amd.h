@@ -1040,6 +1040,72 @@ int y4_rcrop_u8_f32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs_host,
                     const float* std3_host, float* dst, long long dst_sb, long long dst_sc, long long dst_sh, long long dst_sw,
                     void* workspace, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- RandAugment (what torchvision's RandAugment(num_ops,
+ * magnitude, num_magnitude_bins, interpolation=NEAREST, fill=None) asks of Pillow in the reference's darknet/main_amp.py:
+ * 221-227), on the uint8 RGB S x S crops between the gather above and its normalisation.  The host draws the operations and
+ * turns each magnitude into integers and one float; the device sees only those.  One record per sample and round (40 bytes): */
+#define Y4_RA_IDENTITY 0
+#define Y4_RA_SHEAR_X 1         /* codes 1..5 are one operation on the device: the gather through a[0..5] */
+#define Y4_RA_SHEAR_Y 2
+#define Y4_RA_TRANSLATE_X 3
+#define Y4_RA_TRANSLATE_Y 4
+#define Y4_RA_ROTATE 5
+#define Y4_RA_BRIGHTNESS 6
+#define Y4_RA_COLOR 7
+#define Y4_RA_CONTRAST 8
+#define Y4_RA_SHARPNESS 9
+#define Y4_RA_POSTERIZE 10
+#define Y4_RA_SOLARIZE 11
+#define Y4_RA_AUTOCONTRAST 12
+#define Y4_RA_EQUALIZE 13
+typedef struct y4_randaug_op {
+    int op;                         /* Y4_RA_* */
+    int a[6];                       /* codes 1..5: the inverse affine matrix in 16.16 fixed point, see below */
+    float factor;                   /* codes 6..9: ImageEnhance's factor 1 + m, rounded to fp32 */
+    int bits;                       /* Y4_RA_POSTERIZE: bits kept, 0..8 */
+    int threshold;                  /* Y4_RA_SOLARIZE: ceil of Pillow's threshold; pixels >= it are inverted */
+} y4_randaug_op;
+/* The arithmetic is Pillow 12's for 8-bit RGB, bit for bit.  px is a channel of the pixel, P = S * S.
+ *   codes 1..5  libImaging's affine_fixed: output (x, y) shows input ((a[2] + a[1] y + a[0] x) >> 16, (a[5] + a[4] y + a[3] x)
+ *               >> 16) where that lies inside the image and black elsewhere (sums in 64 bits).  The host forms the inverse
+ *               matrix m0..m5 in double (torchvision's _get_inverse_affine_matrix for the shears and translations, Image.rotate's
+ *               for the rotation) and a[i] = FIX(m[i]) for i = 0, 1, 3, 4, a[2] = FIX(m2 + m0 / 2 + m1 / 2), a[5] = FIX(m5 +
+ *               m3 / 2 + m4 / 2), FIX(v) = v * 65536 + 0.5 truncated, floored when negative.
+ *   codes 6..9  ImagingBlend in fp32 without fused multiply-add: t = deg + factor * (px - deg); 0 <= factor <= 1: (uint8)t;
+ *               else t <= 0 -> 0, t >= 255 -> 255, else (uint8)t.  deg is 0 (Brightness); L = (19595 R + 38470 G + 7471 B +
+ *               32768) >> 16 of the pixel (Color); (int)(sum of L over the image / P + 0.5), the sum exact, the division in
+ *               double (Contrast); ImageFilter.SMOOTH of the image (Sharpness): on the one-pixel frame the pixel itself, inside
+ *               ss = 0.5 + row(y + 1) + row(y) + row(y - 1) added in that order, row(r) = (px[r][x - 1] k + px[r][x] c) +
+ *               px[r][x + 1] k with k = 1.0f / 13.0f and c = 5.0f / 13.0f on row y, k elsewhere, clipped like t.
+ *   code 10     px & ~(2^(8 - bits) - 1).        code 11: px < threshold ? px : 255 - px.
+ *   code 12     per channel, lo / hi the first / last occupied histogram bin: the identity when hi <= lo, else scale = 255.0 /
+ *               (hi - lo), offset = -lo * scale, lut[i] = clip((int)(i * scale + offset), 0, 255) in unfused double.
+ *   code 13     per channel with histogram h: the identity when at most one bin is occupied or step = (P - h[hi]) / 255 is 0
+ *               (integer division), else lut[i] = min((step / 2 + h[0] + .. + h[i - 1]) / step, 255).
+ *
+ * y4_rcrop_randaug_u8_f32 is y4_rcrop_u8_f32 with the operations in between.  With plain[b] the uint8 RGB S x S image the
+ * gather produces for job b (window, channel order, flip; no paste) and aug[b] that image after ops[b][0], .., ops[b][n_ops - 1]
+ * in order, output pixel (b, oy, ox) is aug[paste_from] inside job b's paste rectangle and aug[b] outside it, normalised and
+ * stored exactly as y4_rcrop_u8_f32 does.  The table ops[n][n_ops] is passed twice like the job table.  n_ops = 0: the two
+ * launches and the bits of y4_rcrop_u8_f32; the op table and the second workspace are not looked at and may be NULL.
+ * Otherwise: the coefficient launch; the gather, into a uint8 batch [n][S][S][3]; per round at most two launches over the
+ * whole batch -- per-sample 3 x 256 histograms and the sum of L by integer atomics (order independent; only in a round where
+ * the host sees a code 8, 12 or 13), then the operation, from one uint8 batch into the other (never in place: codes 1..5 and
+ * 9 read neighbours).  The last round evaluates "the operation of sample j at pixel p" for j = b or j = paste_from and writes
+ * the normalised fp32 result; no final uint8 batch exists.  2 + 2 n_ops launches at most, no allocation, no synchronisation.
+ * workspace2 (16-byte aligned) holds the two uint8 batches, each n * S * S * 3 bytes rounded up to 256, and the statistics,
+ * n * n_ops * 772 int32 (3 x 256 counts, the sum of L, three words of padding): y4_randaug_workspace, 0 for n outside
+ * [1, 65535], S outside [1, 4096] or n_ops outside [1, 8].
+ * Errors before any launch: everything y4_rcrop_u8_f32 reports; n_ops outside [0, 8] Y4_ERR_SHAPE; with n_ops > 0: a NULL op
+ * table or workspace2 Y4_ERR_NULL, S > 4096 (above it 16.16 coordinates and the 32-bit sum of L, at most 255 * 4096^2, leave
+ * their range), a workspace2 that is not 16-byte aligned, a code outside 0..13, bits outside [0, 8] in a code 10 record or a
+ * factor that is not finite Y4_ERR_SHAPE; ws2_bytes < y4_randaug_workspace(n, S, n_ops) Y4_ERR_WORKSPACE. */
+size_t y4_randaug_workspace(int n, int S, int n_ops);
+int y4_rcrop_randaug_u8_f32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs_host, int n, int S, const float* mean3_host,
+                            const float* std3_host, float* dst, long long dst_sb, long long dst_sc, long long dst_sh,
+                            long long dst_sw, void* workspace, size_t ws_bytes, const y4_randaug_op* ops_dev,
+                            const y4_randaug_op* ops_host, int n_ops, void* workspace2, size_t ws2_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

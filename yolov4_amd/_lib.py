@@ -157,6 +157,8 @@ PROTOTYPES = {
     'y4_rcrop_workspace': (Z, [P, I, I]),
     'y4_rcrop_coeffs_i32': (I, [P, P, I, I, P, Z, P]),
     'y4_rcrop_u8_f32': (I, [P, P, I, I, P, P, P, L, L, L, L, P, Z, P]),
+    'y4_randaug_workspace': (Z, [I, I, I]),
+    'y4_rcrop_randaug_u8_f32': (I, [P, P, I, I, P, P, P, L, L, L, L, P, Z, P, P, I, P, Z, P]),
 }
 
 ERR_FORMAT, ERR_UNSUPPORTED = 6, 7
@@ -224,6 +226,11 @@ class RcropJob(ctypes.Structure):
                 ('crop_x', c_int), ('crop_y', c_int), ('crop_w', c_int), ('crop_h', c_int), ('res_w', c_int), ('res_h', c_int),
                 ('win_x', c_int), ('win_y', c_int), ('flip', c_int), ('paste_from', c_int), ('paste_x0', c_int),
                 ('paste_y0', c_int), ('paste_x1', c_int), ('paste_y1', c_int), ('ws_offset', c_longlong)]
+
+
+class RandaugOp(ctypes.Structure):
+    """y4_randaug_op (40 bytes)"""
+    _fields_ = [('op', c_int), ('a', c_int * 6), ('factor', c_float), ('bits', c_int), ('threshold', c_int)]
 
 
 _lib = None

@@ -15,26 +15,10 @@
 // source row of a tile, not once per output row.  No LDS, no MFMA; byte loads, int32 multiply-adds, coalesced plane stores.
 // CutMix: a batch with a paste doubles the grid's z; the second half writes, inside each sample's rectangle, the pixels its
 // partner's record and tables give at the same place, the first half everything outside it.
-#include <limits.h>
-#include <math.h>
-
-#include "common.h"
+// The gather's body lives in rcrop_gather_body.inc: randaug.hip compiles the same text with a uint8 store for RandAugment.
+#include "rcrop_gather.h"
 
 namespace {
-
-constexpr int kTileX = 64;          // output columns per block = threads per block (one wave)
-constexpr int kTileY = 6;           // output rows per block: 18 int32 accumulators per thread (6 beat 4, 8, 12, 16)
-constexpr int kPrecBits = 22;       // Pillow's PRECISION_BITS for 8-bit pixels (32 - 8 - 2)
-constexpr int kMaxSide = 65535;
-
-// taps per output index of one axis: Pillow's ksize for the bilinear filter (support 1.0)
-__host__ __device__ inline int rc_ksize(int in, int out) {
-    const double scale = (double)in / (double)out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    return (int)ceil(fs) * 2 + 1;
-}
-// int32 words of one axis' table: bounds[S][2], then k[S][ksize]
-__host__ __device__ inline long long rc_axis_words(int S, int ksize) { return (long long)S * (2 + ksize); }
 
 size_t rc_job_bytes(const y4_rcrop_job& j, int S) {
     const long long words = rc_axis_words(S, rc_ksize(j.crop_w, j.res_w)) + rc_axis_words(S, rc_ksize(j.crop_h, j.res_h));
@@ -84,107 +68,19 @@ rcrop_coeffs_kernel(const y4_rcrop_job* __restrict__ jobs, int S, int* __restric
     base[2ll * i + 1] = n;
 }
 
-struct rc_norm {
-    float mean[3], std[3];
-};
-
-__device__ __forceinline__ int rc_clip8(int v) {
-    v >>= kPrecBits;
-    return v < 0 ? 0 : (v > 255 ? 255 : v);
-}
-
 __global__ void __launch_bounds__(kTileX)
 rcrop_gather_kernel(const y4_rcrop_job* __restrict__ jobs, int n, int S, const int* __restrict__ ws, rc_norm nm,
                     float* __restrict__ dst, long long dsb, long long dsc, long long dsh, long long dsw) {
-    // blockIdx.z < n: the sample's own pixels, outside its paste rectangle; n + b (launched only when the batch has a paste):
-    // the partner's pixels at the same place, inside the rectangle.  A block without a pixel of its kind leaves at once.
-    const int pass = blockIdx.z >= (unsigned)n ? 1 : 0;
-    const int tx0 = blockIdx.x * kTileX, ty0 = blockIdx.y * kTileY, b = blockIdx.z - pass * n;
-    const int tx1 = min(tx0 + kTileX, S), ty1 = min(ty0 + kTileY, S);
-    const int ox = tx0 + threadIdx.x;
-    const y4_rcrop_job self = jobs[b];
-    int px0 = 0, px1 = 0, py0 = 0, py1 = 0;                   // the paste rectangle; empty without a partner
-    if (self.paste_from >= 0) { px0 = self.paste_x0; px1 = self.paste_x1; py0 = self.paste_y0; py1 = self.paste_y1; }
-    // the tile's share of the rectangle
-    const int ix0 = max(tx0, px0), ix1 = min(tx1, px1), iy0 = max(ty0, py0), iy1 = min(ty1, py1);
-    const bool any_in = ix0 < ix1 && iy0 < iy1;
-    const bool rows_in = any_in && iy0 == ty0 && iy1 == ty1;  // every row of the tile crosses the rectangle
-    const bool all_in = rows_in && ix0 == tx0 && ix1 == tx1;
-    const bool in_x = ox >= px0 && ox < px1;
-
-    if (pass == 0 ? all_in : !any_in) return;                 // block-uniform
-    const y4_rcrop_job jb = pass ? jobs[self.paste_from] : self;
-    const int ksx = rc_ksize(jb.crop_w, jb.res_w), ksy = rc_ksize(jb.crop_h, jb.res_h);
-    const int* __restrict__ tabx = ws + jb.ws_offset / 4;
-    const int* __restrict__ taby = tabx + rc_axis_words(S, ksx);
-    const int* __restrict__ ky = taby + 2ll * S;
-
-    int ymin[kTileY], yn[kTileY];                             // block-uniform, statically indexed
-    int ylo = INT_MAX, yhi = 0;
-#pragma unroll
-    for (int j = 0; j < kTileY; ++j) {
-        ymin[j] = 0;
-        yn[j] = 0;
-        if (ty0 + j < S) {
-            ymin[j] = taby[2 * (ty0 + j)];
-            yn[j] = taby[2 * (ty0 + j) + 1];
-            ylo = min(ylo, ymin[j]);
-            yhi = max(yhi, ymin[j] + yn[j]);
-        }
-    }
-
-    if (ox >= S || (pass ? !in_x : (in_x && rows_in))) return;    // (no barrier anywhere in this kernel)
-    const int i = jb.flip ? S - 1 - ox : ox;                  // the window column this output column shows
-    const int xmin = tabx[2 * i], xn = tabx[2 * i + 1];
-    const int* __restrict__ kx = tabx + 2ll * S + (long long)i * ksx;
-    const unsigned char* __restrict__ col =
-        (const unsigned char*)jb.src + (long long)jb.crop_y * jb.src_pitch + 3ll * (jb.crop_x + xmin);
-
-    int acc[kTileY][3];
-#pragma unroll
-    for (int j = 0; j < kTileY; ++j) acc[j][0] = acc[j][1] = acc[j][2] = 1 << (kPrecBits - 1);
-
-    for (int r = ylo; r < yhi; ++r) {                         // rows of the crop
-        const unsigned char* __restrict__ p = col + (long long)r * jb.src_pitch;
-        int h0 = 1 << (kPrecBits - 1), h1 = h0, h2 = h0;
-        for (int t = 0; t < xn; ++t) {
-            const int k = kx[t];
-            h0 += (int)p[3 * t] * k;
-            h1 += (int)p[3 * t + 1] * k;
-            h2 += (int)p[3 * t + 2] * k;
-        }
-        h0 = rc_clip8(h0);                                    // Pillow stores the horizontal pass as uint8
-        h1 = rc_clip8(h1);
-        h2 = rc_clip8(h2);
-#pragma unroll
-        for (int j = 0; j < kTileY; ++j) {
-            const int t = r - ymin[j];
-            if ((unsigned)t < (unsigned)yn[j]) {
-                const int k = ky[(long long)(ty0 + j) * ksy + t];
-                acc[j][0] += h0 * k;
-                acc[j][1] += h1 * k;
-                acc[j][2] += h2 * k;
-            }
-        }
-    }
-
-    float* __restrict__ o = dst + (long long)b * dsb + (long long)ox * dsw;
-#pragma unroll
-    for (int j = 0; j < kTileY; ++j) {
-        const int oy = ty0 + j;
-        if (oy >= S) break;
-        const bool inside = in_x && oy >= py0 && oy < py1;
-        if (inside != (pass == 1)) continue;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {                         // c: output channel; memory channel 2 - c under swap_rb
-            const int v = rc_clip8(jb.swap_rb ? acc[j][2 - c] : acc[j][c]);
-            o[(long long)c * dsc + (long long)oy * dsh] = __fdiv_rn((float)v - nm.mean[c], nm.std[c]);
-        }
-    }
+#define RC_GATHER_U8 0
+#include "rcrop_gather_body.inc"
+#undef RC_GATHER_U8
 }
 
-// every check of the two entry points that concerns the job table; nothing is launched unless this returns Y4_OK
-int rc_check(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs, int n, int S, const void* workspace, size_t ws_bytes) {
+}  // namespace
+
+// every check of the entry points that concerns the job table; nothing is launched unless this returns Y4_OK
+int y4::rcrop_check(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs, int n, int S, const void* workspace,
+                    size_t ws_bytes) {
     if (!jobs_dev || !jobs || !workspace) return Y4_ERR_NULL;
     if (n < 1 || n > 65535 || S < 1 || S > kMaxSide) return Y4_ERR_SHAPE;
     for (int i = 0; i < n; ++i) {
@@ -208,11 +104,27 @@ int rc_check(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs, int n, int 
     return Y4_OK;
 }
 
-void rc_launch_coeffs(const y4_rcrop_job* jobs_dev, int n, int S, void* workspace, hipStream_t st) {
+void y4::rcrop_launch_coeffs(const y4_rcrop_job* jobs_dev, int n, int S, void* workspace, hipStream_t st) {
     hipLaunchKernelGGL(rcrop_coeffs_kernel, dim3((S + 255) / 256, 2, n), dim3(256), 0, st, jobs_dev, S, (int*)workspace);
 }
 
-}  // namespace
+int y4::rcrop_norm(const float* mean3_host, const float* std3_host, rc_norm* nm) {
+    for (int c = 0; c < 3; ++c) {
+        if (!isfinite(mean3_host[c]) || !isfinite(std3_host[c]) || std3_host[c] == 0.0f) return Y4_ERR_SHAPE;
+        nm->mean[c] = mean3_host[c];
+        nm->std[c] = std3_host[c];
+    }
+    return Y4_OK;
+}
+
+void y4::rcrop_launch_gather_f32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs_host, int n, int S,
+                                 const void* workspace, const rc_norm& nm, float* dst, long long dsb, long long dsc,
+                                 long long dsh, long long dsw, hipStream_t st) {
+    bool pastes = false;
+    for (int i = 0; i < n; ++i) pastes = pastes || jobs_host[i].paste_from >= 0;
+    hipLaunchKernelGGL(rcrop_gather_kernel, dim3((S + kTileX - 1) / kTileX, (S + kTileY - 1) / kTileY, pastes ? 2 * n : n),
+                       dim3(kTileX), 0, st, jobs_dev, n, S, (const int*)workspace, nm, dst, dsb, dsc, dsh, dsw);
+}
 
 extern "C" size_t y4_rcrop_workspace(const y4_rcrop_job* jobs_host, int n, int S) {
     if (!jobs_host || n < 1 || S < 1 || S > kMaxSide) return 0;
@@ -227,9 +139,9 @@ extern "C" size_t y4_rcrop_workspace(const y4_rcrop_job* jobs_host, int n, int S
 
 extern "C" int y4_rcrop_coeffs_i32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jobs_host, int n, int S, void* workspace,
                                    size_t ws_bytes, void* stream) {
-    const int rc = rc_check(jobs_dev, jobs_host, n, S, workspace, ws_bytes);
+    const int rc = y4::rcrop_check(jobs_dev, jobs_host, n, S, workspace, ws_bytes);
     if (rc != Y4_OK) return rc;
-    rc_launch_coeffs(jobs_dev, n, S, workspace, y4_stream(stream));
+    y4::rcrop_launch_coeffs(jobs_dev, n, S, workspace, y4_stream(stream));
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
@@ -238,21 +150,14 @@ extern "C" int y4_rcrop_u8_f32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job*
                                const float* mean3_host, const float* std3_host, float* dst, long long dst_sb, long long dst_sc,
                                long long dst_sh, long long dst_sw, void* workspace, size_t ws_bytes, void* stream) {
     if (!mean3_host || !std3_host || !dst) return Y4_ERR_NULL;
-    const int rc = rc_check(jobs_dev, jobs_host, n, S, workspace, ws_bytes);
+    int rc = y4::rcrop_check(jobs_dev, jobs_host, n, S, workspace, ws_bytes);
     if (rc != Y4_OK) return rc;
     rc_norm nm;
-    for (int c = 0; c < 3; ++c) {
-        if (!isfinite(mean3_host[c]) || !isfinite(std3_host[c]) || std3_host[c] == 0.0f) return Y4_ERR_SHAPE;
-        nm.mean[c] = mean3_host[c];
-        nm.std[c] = std3_host[c];
-    }
-    rc_launch_coeffs(jobs_dev, n, S, workspace, y4_stream(stream));
+    rc = y4::rcrop_norm(mean3_host, std3_host, &nm);
+    if (rc != Y4_OK) return rc;
+    y4::rcrop_launch_coeffs(jobs_dev, n, S, workspace, y4_stream(stream));
     Y4_CHECK_LAUNCH();
-    bool pastes = false;
-    for (int i = 0; i < n; ++i) pastes = pastes || jobs_host[i].paste_from >= 0;
-    hipLaunchKernelGGL(rcrop_gather_kernel, dim3((S + kTileX - 1) / kTileX, (S + kTileY - 1) / kTileY, pastes ? 2 * n : n),
-                       dim3(kTileX), 0, y4_stream(stream), jobs_dev, n, S, (const int*)workspace, nm, dst, dst_sb, dst_sc,
-                       dst_sh, dst_sw);
+    y4::rcrop_launch_gather_f32(jobs_dev, jobs_host, n, S, workspace, nm, dst, dst_sb, dst_sc, dst_sh, dst_sw, y4_stream(stream));
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }

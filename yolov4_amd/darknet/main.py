@@ -5,9 +5,11 @@ DATA holds train/ and val/, one sub-directory per class (darknet/data.py).  Same
 lr * batch / 256 (the reference parses --momentum and --weight-decay and then builds Adam without them; so does this script),
 label-smoothed cross entropy, the step LR schedule with warm-up, validation after every epoch, checkpoint.pth.tar and, on a
 new best Prec@1, model_best.pth.tar in the working directory.  The checkpoint's state_dict carries the 'module.' prefix the
-reference's DDP wrapper gives it, which is the form YOLOv4's BACKBONE_PRETRAINED path reads.  Not here: apex amp (fp32 only),
-more than one process, RandAugment.  Beyond the reference: --num-classes, --crop-size, --val-size, --cutmix-prob,
---label-smoothing (the YOLOv4 paper's classifier recipe is CutMix + label smoothing)."""
+reference's DDP wrapper gives it, which is the form YOLOv4's BACKBONE_PRETRAINED path reads.  --randaugment puts
+RandAugment(num_ops=2, magnitude=9) behind the flip: passing it is the reference's recipe (main_amp.py:221-227); it is off by
+default, and --ra-num-ops / --ra-magnitude change its two parameters.  Not here: apex amp (fp32 only), more than one process.
+Beyond the reference: --num-classes, --crop-size, --val-size, --cutmix-prob, --label-smoothing (the YOLOv4 paper's
+classifier recipe is CutMix + label smoothing)."""
 import argparse
 import os
 import shutil
@@ -15,7 +17,7 @@ import shutil
 import torch
 
 from .classifier import CSPDarknet53
-from .data import ImageFolder, ImageNetBatchLoader
+from .data import ImageFolder, ImageNetBatchLoader, RandAugment
 from .loss import CrossEntropyLoss
 from .train import train, validate
 from ..yolo.optim.optimizers.build import FusedAdam
@@ -40,6 +42,9 @@ def parse(argv=None):
     parser.add_argument('--val-size', default=288, type=int)
     parser.add_argument('--cutmix-prob', default=0.0, type=float)
     parser.add_argument('--label-smoothing', default=0.1, type=float)
+    parser.add_argument('--randaugment', action='store_true', help="RandAugment behind the flip: the reference's recipe")
+    parser.add_argument('--ra-num-ops', default=2, type=int, metavar='N', help='operations per image (at most 8)')
+    parser.add_argument('--ra-magnitude', default=9, type=int, metavar='M', help='magnitude bin, 0..30')
     return parser.parse_args(argv)
 
 
@@ -80,7 +85,9 @@ def main(argv=None):
         validate(val_loader, model, criterion)
         return
     train_loader = ImageNetBatchLoader(ImageFolder(os.path.join(args.data, 'train')), args.batch_size, train=True,
-                                       shuffle=True, cutmix_prob=args.cutmix_prob, **common)
+                                       shuffle=True, cutmix_prob=args.cutmix_prob,
+                                       randaugment=RandAugment(args.ra_num_ops, args.ra_magnitude) if args.randaugment else None,
+                                       **common)
     for epoch in range(start_epoch, args.epochs):
         train_loader.set_epoch(epoch)
         train(train_loader, model, criterion, optimizer, epoch, args.lr, print_freq=args.print_freq)
