@@ -1106,6 +1106,30 @@ int y4_rcrop_randaug_u8_f32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jo
                             long long dst_sw, void* workspace, size_t ws_bytes, const y4_randaug_op* ops_dev,
                             const y4_randaug_op* ops_host, int n_ops, void* workspace2, size_t ws2_bytes, void* stream);
 
+/* ---- anchor fitting on label shapes (csrc/anchors.hip) ------------------------------------------
+ * The shape IoU of a label shape (tw, th) and an anchor (aw, ah) is the loss's (y4_yolo_loss_fwd_ex_f32's assignment), in
+ * fp32, unfused, with IEEE division:
+ *     brx = fminf(tw, aw); bry = fminf(th, ah); ai = brx * bry; iou = ai / ((tw * th + aw * ah) - ai)
+ * The best anchor of a shape is the arg-max over the A anchors, lowest index on ties.  Shapes and anchors are finite with
+ * 0 < w, h < 65536 (the caller's duty: device data is not looked at on the host, and there is no NaN branch).
+ * Every sum is an int64 sum of fixed-point values: qw = rint(double(w) * 2^16), qh likewise, qiou = rint(double(iou) * 2^30);
+ * the results are the same bytes for every grid and on every run.
+ *
+ * y4_anchor_assign_f32: one Lloyd assignment pass of wh [N][2] against anchors [A][2] (both on the device).
+ *   assign [N] (may be NULL) the best anchor; best_iou [N] (may be NULL) its IoU; acc [A][5] is zeroed by the call and
+ *   receives per anchor: the number of shapes it is best for, their sum of qw, of qh, of qiou (of the best IoU), and `hits`,
+ *   the number of shapes for which the anchor is the best one or has iou > iou_thresh (strict): the positives the loss's
+ *   iou_thresh rule creates.  With iou_thresh = 1, hits == count.
+ * y4_anchor_fitness_f32: G candidate anchor sets cand [G][A][2] scored against the same shapes in one launch.  out [G][2]
+ *   is zeroed by the call and receives per candidate: the sum over the shapes of the best anchor's qiou, and the number of
+ *   shapes whose best IoU is > thr (strict).
+ * One memset node and one launch each, no allocation, no synchronisation.
+ * Errors before any launch (nothing is written): a NULL wh, anchors / cand or acc / out Y4_ERR_NULL; N outside [1, 2^24],
+ * A outside [1, 32], G outside [1, 65535], or one of those three pointers not 8-byte aligned Y4_ERR_SHAPE. */
+int y4_anchor_assign_f32(const float* wh, int N, const float* anchors, int A, float iou_thresh, unsigned char* assign,
+                         float* best_iou, long long* acc, void* stream);
+int y4_anchor_fitness_f32(const float* wh, int N, const float* cand, int G, int A, float thr, long long* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,8 @@ PROTOTYPES = {
     'y4_rcrop_u8_f32': (I, [P, P, I, I, P, P, P, L, L, L, L, P, Z, P]),
     'y4_randaug_workspace': (Z, [I, I, I]),
     'y4_rcrop_randaug_u8_f32': (I, [P, P, I, I, P, P, P, L, L, L, L, P, Z, P, P, I, P, Z, P]),
+    'y4_anchor_assign_f32': (I, [P, I, P, I, F, P, P, P, P]),
+    'y4_anchor_fitness_f32': (I, [P, I, P, I, I, F, P, P]),
 }
 
 ERR_FORMAT, ERR_UNSUPPORTED = 6, 7

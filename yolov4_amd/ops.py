@@ -2069,3 +2069,41 @@ def coco_accumulate(codes, rank, order, cat_off, cat_off_host, npig_cat, rec_thr
                                    _ptr(ins[5]), int_array([int(v) for v in max_dets]), _ptr(precision), _ptr(recall),
                                    _stream()), 'coco_accumulate')
     return precision, recall
+
+
+# ---------------------------------------------------------------------------------------------------- anchor fitting
+
+def _anchor_dev(t, shape_tail, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise Y4Error(f'{what}: expected a tensor on an MI355X (no CPU fallback)')
+    if t.dtype != torch.float32 or t.dim() != len(shape_tail) + 1 or tuple(t.shape[1:]) != tuple(shape_tail) or t.shape[0] < 1:
+        raise Y4Error(f'{what}: expected float32 [n, {", ".join(str(s) for s in shape_tail)}], got {t.dtype} {tuple(t.shape)}')
+    return t.contiguous()
+
+
+def anchor_assign_raw(wh, anchors, iou_thresh=1.0, want_assign=True, want_iou=True):
+    """y4_anchor_assign_f32 (include/yolov4_amd.h): wh [N,2], anchors [A,2] fp32 on the device ->
+    (assign uint8 [N] or None, best_iou fp32 [N] or None, acc int64 [A,5]) on the device.  No host sync."""
+    wh, anchors = _anchor_dev(wh, (2,), 'anchor_assign wh'), _anchor_dev(anchors, (2,), 'anchor_assign anchors')
+    N, A = int(wh.shape[0]), int(anchors.shape[0])
+    dev = wh.device
+    assign = torch.empty((N,), device=dev, dtype=torch.uint8) if want_assign else None
+    best = torch.empty((N,), device=dev, dtype=torch.float32) if want_iou else None
+    acc = torch.empty((A, 5), device=dev, dtype=torch.int64)
+    check(lib().y4_anchor_assign_f32(_ptr(wh), N, _ptr(anchors), A, float(iou_thresh), _ptr(assign), _ptr(best), _ptr(acc),
+                                     _stream()), 'anchor_assign')
+    return assign, best, acc
+
+
+def anchor_fitness_raw(wh, cand, thr):
+    """y4_anchor_fitness_f32: wh [N,2], cand [G,A,2] fp32 on the device -> out int64 [G,2] on the device (sum of the best
+    anchors' qiou, number of shapes with best IoU > thr).  No host sync."""
+    wh = _anchor_dev(wh, (2,), 'anchor_fitness wh')
+    if not torch.is_tensor(cand) or cand.dim() != 3:
+        raise Y4Error('anchor_fitness cand: expected float32 [G, A, 2] on the device')
+    cand = _anchor_dev(cand, (int(cand.shape[1]), 2), 'anchor_fitness cand')
+    G, A = int(cand.shape[0]), int(cand.shape[1])
+    out = torch.empty((G, 2), device=wh.device, dtype=torch.int64)
+    check(lib().y4_anchor_fitness_f32(_ptr(wh), int(wh.shape[0]), _ptr(cand), G, A, float(thr), _ptr(out), _stream()),
+          'anchor_fitness')
+    return out
