@@ -414,8 +414,10 @@ int y4_yolo_decode_bwd_f32(const float* logits, int ldl, const float* g_output, 
 /* The same three with the YOLOv4 grid-sensitivity factor scale_x_y (Darknet's [yolo] scale_x_y: 1.2 / 1.1 / 1.05 per
  * layer, 2.0 in the scaled models).  s = scale_xy as fp32, h = (s - 1) * 0.5f in fp32, sigma = the fp32 sigmoid:
  *   train: pred[..., 0] = ((sigma_x * s) - h) + i, pred[..., 1] = ((sigma_y * s) - h) + j; output[..., 0:2] stays sigma.
- *   eval : the same centre, times stride.  The tiled kernel evaluates sigma * (s * stride) + stride * (i - h), and
- *          sigma * s + (i - h) in training: other roundings, the same value to a few ulp of its largest addend.
+ *   eval : the same centre, times stride.  With s != 1 the eval centre is evaluated in fp64 from the logit and rounded to fp32
+ *          once: sigma * s - h cancels in the first column / row, where an fp32 sigmoid would be arbitrarily far off relative
+ *          to the result.  In training the tiled kernel evaluates sigma * s + (i - h): other roundings, the same value to a
+ *          few ulp of its largest addend.
  *   bwd  : the g_pred contribution on channels 0 and 1 is s * g_pred.
  * w, h, objectness and classes are untouched.  scale_xy = 1 gives the bits of the entries above (sigma * 1 and x - 0 are
  * exact), which forward here.  scale_xy outside [1, 2], NaN included: Y4_ERR_SHAPE before any launch. */
@@ -428,6 +430,12 @@ int y4_yolo_decode_eval_ex_f32(const float* logits, int ldl, float* out, long lo
 int y4_yolo_decode_bwd_ex_f32(const float* logits, int ldl, const float* g_output, const float* g_pred,
                               float* g_logits, int B, int F, int A, int n_classes,
                               const float* anchors_wh_host, float scale_xy, void* stream);
+/* The eval decode on a rectangular map (letterboxed inference): logits NHWC [B,Fh,Fw,>=A*(5+C)];
+ * out[b, box_off + a*Fh*Fw + j*Fw + i, :], x from the column i < Fw, y from the row j < Fh.  Same kernels, dispatch rule and
+ * arithmetic as y4_yolo_decode_eval_ex_f32, whose bits it gives when Fh == Fw.  box_off + A*Fh*Fw > n_total: Y4_ERR_SHAPE. */
+int y4_yolo_decode_eval_rect_f32(const float* logits, int ldl, float* out, long long n_total, long long box_off,
+                                 int B, int Fh, int Fw, int A, int n_classes, const float* anchors_wh_host,
+                                 float stride, float scale_xy, void* stream);
 
 /* ---------------------------------------------------------------- detection loss
  * Replaces YOLOLoss.build_target + YOLOLoss.forward for one layer,
@@ -691,6 +699,32 @@ int y4_ema_multi_f32(const void* chunks_dev, int nchunks, float one_minus_decay,
  * (transform.py:461): dst[c*dst_sc + y*dst_sh + x*dst_sw], strides in elements (NCHW or NHWC slot of a batch). */
 int y4_preprocess_u8_f32(const void* src, int src_h, int src_w, long long src_pitch_bytes, int swap_rb,
                          float* dst, long long dst_sc, long long dst_sh, long long dst_sw, int S, void* stream);
+
+/* Letterbox (aspect-preserving resize onto a padded canvas) for a whole batch in ONE launch.  One record per image: */
+typedef struct y4_letterbox_src {
+    const void* src;                /* device pointer, uint8 HWC, 3 channels */
+    int h, w;                       /* 1 .. 65535 */
+    long long pitch;                /* bytes, >= 3 * w */
+    int swap_rb;                    /* 1: the source is BGR, the output RGB */
+    int nh, nw;                     /* size the image is resized to, >= 1 */
+    int top, left;                  /* where the resized image lies in the canvas: [top, top + nh) x [left, left + nw) */
+    int reserved;                   /* 48 bytes */
+} y4_letterbox_src;
+/* The table is passed twice, as y4_aug_src is: *_dev is what the kernel reads, *_host the same bytes in host memory, checked
+ * before anything is launched (the caller copies host -> device on the same stream; no synchronisation).
+ * dst[b*dst_sb + c*dst_sc + oy*dst_sh + ox*dst_sw] (strides in elements) for oy < Hc, ox < Wc:
+ *   inside the image's rectangle: what cv2.resize(src, (nw, nh)) gives at (oy - top, ox - left) -- the 8-bit INTER_LINEAR
+ *     arithmetic of y4_preprocess_u8_f32 with scale_x = 1 / (nw / w), scale_y = 1 / (nh / h) formed in double, and the 2x2
+ *     box average when w == 2 nw and h == 2 nh;
+ *   outside: fill;
+ *   then the B/R swap when swap_rb, and value / 255 in fp32 (the stored fill is (float)fill / 255.0f).
+ * With nh = nw = Hc = Wc = S and top = left = 0 this is y4_preprocess_u8_f32, bit for bit.
+ * Errors before any launch: Y4_ERR_NULL for a NULL pointer (a record's src included); Y4_ERR_SHAPE for B outside [1, 65535],
+ * Hc or Wc outside [1, 65535], h or w outside [1, 65535], pitch < 3w, nh or nw < 1, a placement that does not fit the canvas
+ * (top < 0, top + nh > Hc, the same in x), fill outside [0, 255]. */
+int y4_letterbox_batch_u8_f32(const y4_letterbox_src* table_dev, const y4_letterbox_src* table_host, int B,
+                              float* dst, long long dst_sb, long long dst_sc, long long dst_sh, long long dst_sw,
+                              int Hc, int Wc, int fill, void* stream);
 
 /* ---------------------------------------------------------------- training input pipeline
  * The reference's per-sample CPU augmentation (yolo/data/transform.py:385-427 _get_train_item: crop-and-pad with a mean

@@ -99,6 +99,7 @@ PROTOTYPES = {
     'y4_yolo_decode_train_ex_f32': (I, [P, I, P, P, I, I, I, I, P, F, P]),
     'y4_yolo_decode_eval_ex_f32': (I, [P, I, P, L, L, I, I, I, I, P, F, F, P]),
     'y4_yolo_decode_bwd_ex_f32': (I, [P, I, P, P, P, I, I, I, I, P, F, P]),
+    'y4_yolo_decode_eval_rect_f32': (I, [P, I, P, L, L, I, I, I, I, I, P, F, F, P]),
     'y4_yolo_loss_workspace_ex': (Z, [I, I, I, I, I, F]),
     'y4_yolo_loss_fwd_ex_f32': (I, [P, P, P, I, I, I, I, I, F, F, P, I, P, F, F, P, P, P, Z, P]),
     'y4_yolo_loss_bwd_ex_f32': (I, [P, I, P, P, P, I, I, I, I, I, F, F, P, Z, P]),
@@ -133,6 +134,7 @@ PROTOTYPES = {
     'y4_sgd_multi_step_guarded_f32': (I, [P, I, P, I, F, P, P]),
     'y4_ema_multi_f32': (I, [P, I, F, P, P]),
     'y4_preprocess_u8_f32': (I, [P, I, I, L, I, P, L, L, L, I, P]),
+    'y4_letterbox_batch_u8_f32': (I, [P, P, I, P, L, L, L, L, I, I, I, P]),
     'y4_augment_means_u8': (I, [P, P, I, P, P]),
     'y4_augment_mosaic_u8_f32': (I, [P, P, I, P, P, I, P, P, L, L, L, L, I, P]),
     'y4_avgpool_global_fwd_f32': (I, [P, I, P, I, I, I, I, P]),
@@ -182,6 +184,12 @@ class AugSrc(ctypes.Structure):
                 ('crop_left', c_int), ('crop_top', c_int), ('crop_w', c_int), ('crop_h', c_int), ('flip', c_int),
                 ('color', c_int), ('dhue', c_float), ('dsat', c_float), ('dexp', c_float), ('win_x', c_int),
                 ('win_y', c_int)]
+
+
+class LetterboxSrc(ctypes.Structure):
+    """y4_letterbox_src (48 bytes)"""
+    _fields_ = [('src', c_void_p), ('h', c_int), ('w', c_int), ('pitch', c_longlong), ('swap_rb', c_int), ('nh', c_int),
+                ('nw', c_int), ('top', c_int), ('left', c_int), ('reserved', c_int)]
 
 
 class AugSample(ctypes.Structure):

@@ -20,21 +20,32 @@ struct Anchors { float w[16]; float h[16]; };
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // ------------------------------------------------------------------------------------ decode
+// The eval centre with scale_x_y = s != 1, ((sigma * s) - h + cell) * stride with h = (s - 1) / 2, cancels where sigma * s is near
+// h in the first column / row (cell = 0): an fp32 sigmoid that is a few 2^-24 off is then arbitrarily far off RELATIVE to the
+// result.  These two of the 5 + C channels are therefore evaluated in fp64 from the logit and rounded to fp32 once (error
+// 2^-24 of the result itself); s = 1 has no cancellation (sigma + cell >= sigma) and keeps its fp32 code and bits.
+__device__ __forceinline__ float eval_centre64(float v, float sxy, float hxy, int cell, float stride) {
+    const double sg = 1.0 / (1.0 + exp(-(double)v));
+    return (float)((((sg * (double)sxy) - (double)hxy) + (double)cell) * (double)stride);
+}
+
 // one block sweeps pixels; thread t <-> logit channel t = a*n_ch + ch of that pixel
-template <bool EVAL>
+// RECT: the map is Fh rows of F columns (eval only); without it Fh_arg is not read and the code is the square form's
+template <bool EVAL, bool RECT = false>
 __global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restrict__ logits, long long ldl,
                                                           float* __restrict__ output, float* __restrict__ pred,
                                                           long long n_total, long long box_off, float stride,
                                                           int B, int F, int A, int n_ch, Anchors anc,
-                                                          float sxy, float hxy) {
-    const long long npix = (long long)B * F * F;
+                                                          float sxy, float hxy, int Fh_arg) {
+    const int Fh = RECT ? Fh_arg : F;
+    const long long npix = (long long)B * Fh * F;
     const int nt = A * n_ch;
     for (int t = threadIdx.x; t < nt; t += blockDim.x) {
         const int a = t / n_ch, ch = t - a * n_ch;
         for (long long p = blockIdx.x; p < npix; p += gridDim.x) {
             const int i = (int)(p % F);
-            const int j = (int)((p / F) % F);
-            const long long b = p / ((long long)F * F);
+            const int j = (int)((p / F) % Fh);
+            const long long b = p / ((long long)Fh * F);
             const float v = logits[p * ldl + t];
             float o = v, pv = v;
             if (ch != 2 && ch != 3) { o = sigmoidf_(v); pv = o; }
@@ -45,7 +56,9 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restric
             else if (ch == 3) pv = expf(v) * anc.h[a];
             if (EVAL) {
                 if (ch < 4) pv = pv * stride;
-                output[(b * n_total + box_off + ((long long)a * F + j) * F + i) * n_ch + ch] = pv;
+                // scale_x_y != 1 (eval): the centre in fp64, rounded once (see eval_centre64)
+                if (ch < 2 && sxy != 1.0f) pv = eval_centre64(v, sxy, hxy, ch == 0 ? i : j, stride);
+                output[(b * n_total + box_off + ((long long)a * Fh + j) * F + i) * n_ch + ch] = pv;
             } else {
                 const long long cell = ((b * A + a) * F + j) * F + i;
                 output[cell * n_ch + ch] = o;
@@ -68,18 +81,20 @@ __global__ __launch_bounds__(256) void yolo_decode_kernel(const float* __restric
 // 4.6 - 4.9 TB/s algorithmic on the 76 x 76 layer at bs = 32 (rows of 32 pixels; 16 on small maps for occupancy).
 // SCALED: scale_x_y != 1.  The instance without it has s = 1, h = 0 folded away at compile time: the default path runs the
 // code it always ran (a run-time s = 1 gave the same bits but measured 6 % slower in the eval decode of bench.py).
-template <bool EVAL, int DEC_TP, bool SCALED>              // DEC_TP pixels per tile: DEC_TP x 256 floats of LDS
+// RECT (eval only): Fh_arg rows of F columns; pixel p of an image is (j, i) = (p / F, p % F) either way, so only the pixel
+// count differs.  The square instances do not read Fh_arg: their code is what it was before the option existed.
+template <bool EVAL, int DEC_TP, bool SCALED, bool RECT = false>     // DEC_TP pixels per tile: DEC_TP x 256 floats of LDS
 __global__ __launch_bounds__(256) void yolo_decode_tiled_kernel(const float* __restrict__ logits, long long ldl,
                                                                 float* __restrict__ output, float* __restrict__ pred,
                                                                 long long n_total, long long box_off, float stride,
                                                                 int F, int A, int n_ch, Anchors anc, int tiles_per_img,
-                                                                float sxy_arg, float hxy_arg) {
+                                                                float sxy_arg, float hxy_arg, int Fh_arg) {
     const float sxy = SCALED ? sxy_arg : 1.0f, hxy = SCALED ? hxy_arg : 0.0f;
     __shared__ __attribute__((aligned(16))) float tile[DEC_TP][256];
     __shared__ __attribute__((aligned(16))) float predt[EVAL ? 1 : 4][DEC_TP][4];      // train: decoded boxes per anchor
     const int tid = threadIdx.x;
     const int b = blockIdx.x / tiles_per_img, t = blockIdx.x - b * tiles_per_img;
-    const int FF = F * F;
+    const int FF = (RECT ? Fh_arg : F) * F;
     const int p0 = t * DEC_TP;
     const int cnt = FF - p0 < DEC_TP ? FF - p0 : DEC_TP;
     const int nt = A * n_ch;
@@ -135,6 +150,20 @@ __global__ __launch_bounds__(256) void yolo_decode_tiled_kernel(const float* __r
             }
         }
         *reinterpret_cast<f32x4*>(&tile[r][4 * col4]) = o;
+    }
+    if (EVAL && SCALED) {
+        // the 2 * A centres of each of the tile's pixels again, in fp64 (eval_centre64): one element per thread (cnt <= 32,
+        // A <= 4), its logit re-read from the row phase 1 has just loaded; a barrier of its own, in these instances only
+        __syncthreads();
+        const int per = 2 * A;
+        if (tid < cnt * per) {
+            const int r = tid / per, q = tid - r * per;
+            const int a = q >> 1, ch = q & 1;
+            const int pix = p0 + r;
+            const int j = pix / F, i = pix - j * F;
+            const float v = logits[((long long)b * FF + pix) * ldl + a * n_ch + ch];
+            tile[r][a * n_ch + ch] = eval_centre64(v, sxy, hxy, ch ? j : i, stride);
+        }
     }
     __syncthreads();
     // ---- phase 2
@@ -1610,13 +1639,13 @@ int y4_yolo_decode_train_ex_f32(const float* logits, int ldl, float* output, flo
         auto kern = tp == 16 ? (sc ? yolo_decode_tiled_kernel<false, 16, true> : yolo_decode_tiled_kernel<false, 16, false>)
                              : (sc ? yolo_decode_tiled_kernel<false, 32, true> : yolo_decode_tiled_kernel<false, 32, false>);
         hipLaunchKernelGGL(kern, dim3((unsigned)(B * tpi)), dim3(256), 0, y4_stream(stream), logits,
-                           (long long)ldl, output, pred, 0ll, 0ll, 1.0f, F, A, n_ch, anc, (int)tpi, scale_xy, hxy);
+                           (long long)ldl, output, pred, 0ll, 0ll, 1.0f, F, A, n_ch, anc, (int)tpi, scale_xy, hxy, F);
         Y4_CHECK_LAUNCH();
         return Y4_OK;
     }
     hipLaunchKernelGGL(yolo_decode_kernel<false>, dim3((unsigned)(npix < 8192 ? npix : 8192)), dim3(256), 0,
                        y4_stream(stream), logits, (long long)ldl, output, pred, 0ll, 0ll, 1.0f, B, F, A, n_ch, anc,
-                       scale_xy, hxy);
+                       scale_xy, hxy, F);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
@@ -1646,13 +1675,45 @@ int y4_yolo_decode_eval_ex_f32(const float* logits, int ldl, float* out, long lo
                              : (sc ? yolo_decode_tiled_kernel<true, 32, true> : yolo_decode_tiled_kernel<true, 32, false>);
         hipLaunchKernelGGL(kern, dim3((unsigned)(B * tpi)), dim3(256), 0, y4_stream(stream), logits,
                            (long long)ldl, out, (float*)nullptr, n_total, box_off, stride, F, A, n_ch, anc, (int)tpi,
-                           scale_xy, hxy);
+                           scale_xy, hxy, F);
         Y4_CHECK_LAUNCH();
         return Y4_OK;
     }
     hipLaunchKernelGGL(yolo_decode_kernel<true>, dim3((unsigned)(npix < 8192 ? npix : 8192)), dim3(256), 0,
                        y4_stream(stream), logits, (long long)ldl, out, (float*)nullptr, n_total, box_off, stride, B, F,
-                       A, n_ch, anc, scale_xy, hxy);
+                       A, n_ch, anc, scale_xy, hxy, F);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+
+int y4_yolo_decode_eval_rect_f32(const float* logits, int ldl, float* out, long long n_total, long long box_off,
+                                 int B, int Fh, int Fw, int A, int n_classes, const float* anchors_wh_host,
+                                 float stride, float scale_xy, void* stream) {
+    if (!logits || !out) return Y4_ERR_NULL;
+    const int n_ch = 5 + n_classes;
+    Anchors anc;
+    if (B <= 0 || Fh <= 0 || Fw <= 0 || A <= 0 || n_classes <= 0 || ldl < A * n_ch || !fill_anchors(anc, anchors_wh_host, A) ||
+        !scale_xy_ok(scale_xy))
+        return Y4_ERR_SHAPE;
+    const long long FF = (long long)Fh * Fw;
+    if (FF >= (1ll << 31) || box_off < 0 || box_off + (long long)A * FF > n_total) return Y4_ERR_SHAPE;
+    const float hxy = (scale_xy - 1.0f) * 0.5f;
+    const long long npix = (long long)B * FF;
+    const int tp = decode_tp(npix);
+    const long long tpi = (FF + tp - 1) / tp;
+    if (decode_tiled_ok(logits, ldl, A, n_ch, out, nullptr) && (long long)B * tpi < (1ll << 31)) {
+        const bool sc = scale_xy != 1.0f;
+        auto kern = tp == 16 ? (sc ? yolo_decode_tiled_kernel<true, 16, true, true> : yolo_decode_tiled_kernel<true, 16, false, true>)
+                             : (sc ? yolo_decode_tiled_kernel<true, 32, true, true> : yolo_decode_tiled_kernel<true, 32, false, true>);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(B * tpi)), dim3(256), 0, y4_stream(stream), logits,
+                           (long long)ldl, out, (float*)nullptr, n_total, box_off, stride, Fw, A, n_ch, anc, (int)tpi,
+                           scale_xy, hxy, Fh);
+        Y4_CHECK_LAUNCH();
+        return Y4_OK;
+    }
+    hipLaunchKernelGGL((yolo_decode_kernel<true, true>), dim3((unsigned)(npix < 8192 ? npix : 8192)), dim3(256), 0,
+                       y4_stream(stream), logits, (long long)ldl, out, (float*)nullptr, n_total, box_off, stride, B, Fw,
+                       A, n_ch, anc, scale_xy, hxy, Fh);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }

@@ -4,6 +4,9 @@
     decode (data/jpeg.py) -> val_batch -> model (eval) -> postprocess -> yolobox2yxyx -> draw_detections on the
     ORIGINAL-size image (util/vis.py) -> encode_jpeg_batch (data/jpeg_enc.py)
 
+With `letterbox` ('square' | 'rect') the input keeps the image's aspect on a grey canvas instead (letterbox_batch, one launch per
+batch; 'rect': a canvas only as large as the batch needs) and boxes come back through letterbox2yxyx, clipped to the image.
+
 Per batch the device work is a handful of launches, and the host waits twice: postprocess's one read of the detection counts
 (the detections themselves come back in the same wait) and the encoder's one copy of the coefficients.
 
@@ -21,8 +24,9 @@ import torch
 from ._lib import Y4Error
 from .yolo.data.jpeg import decode_jpeg_batch
 from .yolo.data.jpeg_enc import encode_jpeg_batch
-from .yolo.data.transform import val_batch
-from .yolo.util.utils import NMSOptions, postprocess, postprocess_nms, yolobox2yxyx
+from .yolo.data.transform import letterbox_batch, letterbox_mode, val_batch
+from .yolo.model.yololayer import layer_strides
+from .yolo.util.utils import NMSOptions, letterbox2yxyx, postprocess, postprocess_nms, yolobox2yxyx
 from .yolo.util.vis import class_colors, draw_detections
 
 LINE_WIDTH = 3          # the reference's show_bbox
@@ -45,7 +49,7 @@ def _read(source):
 
 @torch.no_grad()
 def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None, draw=True, encode=True, batch=8,
-                  nms_options=None):
+                  nms_options=None, letterbox=None):
     """sources: JPEG bytes, paths, or [h, w, 3] uint8 BGR device tensors, in any mix -> one dict per source:
       detections  float64 ndarray [n, 7]: (y1, x1, y2, x2, obj, cls_conf, cls) in SOURCE pixels, postprocess's order
       image       [h, w, 3] uint8 BGR device tensor of the source's size, the detections drawn on it when `draw`
@@ -54,9 +58,13 @@ def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None
     conf_thre / nms_thre default to cfg['TEST']['CONFTHRE'] / ['NMSTHRE'] (None or negative, the reference's rule).  The
     label is '<name> <cls_conf:.2f>'; without `names` the class index stands for the name.  The model is run in eval mode, in
     batches of `batch` images, and left in eval mode.  `nms_options` (an NMSOptions or a dict of postprocess_nms's keywords):
-    DIoU- / Soft- / class-agnostic NMS and the per-image cap; None is the reference's postprocess."""
+    DIoU- / Soft- / class-agnostic NMS and the per-image cap; None is the reference's postprocess.
+    `letterbox`: None stretches every image to S x S (the reference's rule); 'square' | 'rect' keep its aspect on a grey
+    canvas, S x S or -- chosen per chunk of `batch` sources -- only as large as the chunk needs, and clip boxes to the image."""
     if nms_options is not None and not isinstance(nms_options, dict):
         nms_options = nms_options.kwargs()
+    letterbox = letterbox_mode(letterbox)
+    max_stride = max(layer_strides(cfg['MODEL'], [8, 16, 32])) if letterbox is not None else None
     conf_thre = cfg['TEST']['CONFTHRE'] if conf_thre is None or conf_thre < 0 else conf_thre
     nms_thre = cfg['TEST']['NMSTHRE'] if nms_thre is None or nms_thre < 0 else nms_thre
     img_size = int(cfg['TEST']['IMGSIZE'])
@@ -81,7 +89,10 @@ def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None
                 if not (s.is_cuda and s.dtype == torch.uint8 and s.dim() == 3 and s.shape[2] == 3):
                     raise Y4Error('source %d: a tensor source is a [h, w, 3] uint8 BGR device tensor' % (start + k))
                 images[k] = s.clone(memory_format=torch.contiguous_format)
-        x, infos = val_batch(images, img_size)
+        if letterbox is None:
+            x, infos = val_batch(images, img_size)
+        else:
+            x, infos = letterbox_batch(images, img_size, letterbox, max_stride)
         if nms_options is None:
             dets = postprocess(model(x), num_classes, conf_thre=conf_thre, nms_thre=nms_thre)
         else:
@@ -95,7 +106,10 @@ def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None
             r = rows[at:at + n]
             at += n
             # the reference hands (y1, x1, y2, x2) = postprocess's columns 1, 0, 3, 2 to yolobox2yxyx
-            y1, x1, y2, x2 = yolobox2yxyx([r[:, 1], r[:, 0], r[:, 3], r[:, 2]], info[:4])
+            if letterbox is None:
+                y1, x1, y2, x2 = yolobox2yxyx([r[:, 1], r[:, 0], r[:, 3], r[:, 2]], info[:4])
+            else:
+                y1, x1, y2, x2 = letterbox2yxyx([r[:, 1], r[:, 0], r[:, 3], r[:, 2]], info)
             out_rows.append(np.concatenate([np.stack([y1, x1, y2, x2], axis=1), r[:, 4:7]], axis=1).reshape(-1, 7))
             cls = r[:, 6].astype(np.int64)
             # int() truncation like the reference's drawing code; a non-finite box (an untrained net) is pinned far outside
@@ -151,7 +165,15 @@ def build_parser():
     ap.add_argument('--nms-sigma', type=float, default=None)
     ap.add_argument('--agnostic-nms', action='store_true', default=None)
     ap.add_argument('--max-det', type=int, default=None)
+    # a flag that is given overrides the cfg's TEST.LETTERBOX (off | square | rect; absent: off, the reference's stretch)
+    ap.add_argument('--letterbox', choices=['off', 'square', 'rect'], default=None)
     return ap
+
+
+def letterbox_from_args(args, cfg):
+    """--letterbox when given, else the cfg's optional TEST.LETTERBOX; None for 'off' / absent."""
+    v = args.letterbox if args.letterbox is not None else (cfg.get('TEST') or {}).get('LETTERBOX')
+    return letterbox_mode(v)
 
 
 def nms_options_from_args(args, cfg):
@@ -191,7 +213,7 @@ def main(argv=None):
     save_dir = increment_path(os.path.join(args.dest, 'exp'))
     os.makedirs(save_dir)
     out = detect_images(model, cfg, paths, args.conf_thre, args.nms_thre, names=args.names, batch=args.batch,
-                        nms_options=nms_options_from_args(args, cfg))
+                        nms_options=nms_options_from_args(args, cfg), letterbox=letterbox_from_args(args, cfg))
     for path, r in zip(paths, out):
         target = os.path.join(save_dir, os.path.splitext(os.path.basename(path))[0] + '.jpg')
         with open(target, 'wb') as f:

@@ -1753,15 +1753,19 @@ def yolo_decode_eval(logits, anchors_wh, n_classes, stride, out=None, n_total=No
     L = lib()
     scale_xy = check_scale_xy(scale_xy)
     _require_gpu(logits, 'YOLOLayer input')
-    B, ch, F, _ = logits.shape
+    B, ch, F, Fw = logits.shape
     n_ch = 5 + n_classes
     A = ch // n_ch
     logits, ldl = as_nhwc(logits, need_vec4=False)
     if out is None:
-        n_total = A * F * F
+        n_total = A * F * Fw
         out = torch.empty((B, n_total, n_ch), device=logits.device, dtype=torch.float32)
         box_off = 0
     anc = float_array([v for wh in anchors_wh for v in wh])
+    if F != Fw:                                            # a rectangular map (letterboxed inference): F rows of Fw columns
+        check(L.y4_yolo_decode_eval_rect_f32(_ptr(logits), ldl, _ptr(out), n_total, box_off, B, F, Fw, A, n_classes, anc,
+                                             float(stride), scale_xy, _stream()), 'yolo_decode_eval_rect')
+        return out
     check(L.y4_yolo_decode_eval_ex_f32(_ptr(logits), ldl, _ptr(out), n_total, box_off, B, F, A, n_classes, anc,
                                        float(stride), scale_xy, _stream()), 'yolo_decode_eval')
     return out

@@ -16,7 +16,9 @@ import numpy as np
 import torch
 
 from .jpeg import MAX_WORKERS, decode_entropy_batch, decode_jpeg_batch, entropy_batch
-from .transform import pad_labels, sample_train_params, train_batch, val_batch
+from .transform import (letterbox_batch, letterbox_labels, letterbox_mode, pad_labels, sample_train_params, train_batch,
+                        val_batch)
+from ..model.yololayer import layer_strides
 
 
 class COCODataset(object):
@@ -41,6 +43,7 @@ class COCODataset(object):
         with open(self.annotation_file, 'r') as f:
             doc = json.load(f)
         self.ids = [im['id'] for im in doc.get('images', [])]
+        self._sizes = [(im.get('height'), im.get('width')) for im in doc.get('images', [])]
         self.class_ids = sorted(c['id'] for c in doc.get('categories', []))
         self._class_of = {}
         for k, c in enumerate(self.class_ids):
@@ -58,6 +61,13 @@ class COCODataset(object):
         if not os.path.isfile(path):
             raise FileNotFoundError(path)
         return path
+
+    def img_hw(self, index):
+        """(height, width) of image `index` as the annotation file states them; no image is read"""
+        h, w = self._sizes[index]
+        if not h or not w:
+            raise ValueError('image %r has no height / width in %s' % (self.ids[index], self.annotation_file))
+        return int(h), int(w)
 
     def get_labels(self, index):
         """[K, 5] float64 rows (x, y, w, h, class) of image `index` (a fresh copy; K may be 0)"""
@@ -126,10 +136,19 @@ class COCOBatchLoader(object):
     Training (dataset.is_train): mosaic by cfg['AUGMENTATION']['IS_MOSAIC'], three extra images with at least one box each
     per sample, every draw from `random.Random` seeded with (seed, epoch, batch): the same seed gives the same batches.
     shuffle permutes the images per epoch (`set_epoch`); rank / world_size take every world_size-th image of that order.
-    Host work (file reads, Huffman decoding on `workers` threads, at most 16) runs one batch ahead of the device work."""
+    Host work (file reads, Huffman decoding on `workers` threads, at most 16) runs one batch ahead of the device work.
 
-    def __init__(self, dataset, batch_size, cfg, shuffle=False, seed=0, workers=8, rank=0, world_size=1, fallback=None):
+    Validation with letterbox = 'square' | 'rect' (None: the reference's stretch to S x S): the input is `letterbox_batch`'s
+    [B, 3, Hc, Wc], labels are mapped onto the canvas, img_info rows are [h, w, nh, nw, img_id, index] and target['pad'] holds B
+    rows of (top, left), which validate() hands to detections_to_coco.  'rect' without shuffle orders the images by h / w (from
+    the annotation file; no image is read for it) so that a batch's canvas is tight."""
+
+    def __init__(self, dataset, batch_size, cfg, shuffle=False, seed=0, workers=8, rank=0, world_size=1, fallback=None,
+                 letterbox=None):
         assert batch_size >= 1 and 0 <= rank < world_size
+        self.letterbox = letterbox_mode(letterbox)
+        if self.letterbox is not None and dataset.is_train:
+            raise ValueError('letterbox is an inference option: the training pipeline stays square')
         self.dataset, self.batch_size, self.cfg = dataset, int(batch_size), cfg
         self.shuffle, self.seed, self.epoch = bool(shuffle), int(seed), 0
         self.workers = max(1, min(int(workers), MAX_WORKERS))
@@ -142,6 +161,9 @@ class COCOBatchLoader(object):
         order = list(range(len(self.dataset)))
         if self.shuffle:
             random.Random(self.seed * 1000003 + self.epoch).shuffle(order)
+        elif self.letterbox == 'rect':
+            aspect = [h / w for h, w in (self.dataset.img_hw(i) for i in order)]
+            order.sort(key=lambda i: aspect[i])            # stable: equal aspects keep the file's order
         return order[self.rank::self.world_size]
 
     def __len__(self):
@@ -193,6 +215,7 @@ class COCOBatchLoader(object):
                 if b + 1 < n:
                     pending = ahead.submit(self._host_batch, order, b + 1, pool)
                 S = int(ds.get_img_size())                  # per batch: set_img_size() between batches takes effect
+                pad = None
                 imgs = decode_entropy_batch(hb)
                 at, items = 0, []
                 for g, bb in zip(groups, boxes):
@@ -203,6 +226,15 @@ class COCOBatchLoader(object):
                               for il, bl in items]
                     x, labels = train_batch(items, S, self.cfg, params=params)
                     info = [[ds.ids[i], i] for i in indices]
+                elif self.letterbox is not None:
+                    G = max(layer_strides(self.cfg['MODEL'], [8, 16, 32]))
+                    x, infos = letterbox_batch([il[0] for il, _ in items], S, self.letterbox, G)
+                    labels = np.zeros((len(items), max_labels, 5), dtype=np.float64)
+                    for k, ((_, bl), inf) in enumerate(zip(items, infos)):
+                        labels[k] = pad_labels(letterbox_labels(bl[0], inf), max_labels)
+                    labels = torch.from_numpy(labels)
+                    info = [inf[:4] + [ds.ids[i], i] for inf, i in zip(infos, indices)]
+                    pad = [inf[4:6] for inf in infos]
                 else:
                     x, infos = val_batch([il[0] for il, _ in items], S)
                     labels = np.zeros((len(items), max_labels, 5), dtype=np.float64)
@@ -215,4 +247,7 @@ class COCOBatchLoader(object):
                         labels[k] = pad_labels(bx, max_labels)
                     labels = torch.from_numpy(labels)
                     info = [inf + [ds.ids[i], i] for inf, i in zip(infos, indices)]
-                yield x, {'padded_labels': labels, 'img_info': info}
+                target = {'padded_labels': labels, 'img_info': info}
+                if pad is not None:
+                    target['pad'] = pad                     # letterboxed input: B rows of (top, left)
+                yield x, target

@@ -22,7 +22,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from ..._lib import AugSample, AugSrc, check, lib
+from ..._lib import AugSample, AugSrc, LetterboxSrc, check, lib
 
 
 def _stream():
@@ -60,6 +60,102 @@ def val_batch(imgs, img_size, device=None):
     out = torch.empty((len(imgs), 3, img_size, img_size), dtype=torch.float32, device=device)
     infos = [image_resize_into(im, out[i]) for i, im in enumerate(imgs)]
     return out, infos
+
+
+# ------------------------------------------------------------------------------------------------ letterbox (opt-in)
+# Aspect-preserving inference input: the image is resized so that its longer side is S and centred on a grey canvas, either
+# S x S ('square') or only as large as the batch needs, rounded up to the model's largest stride ('rect').  The reference has
+# no such mode (its evaluation stretches to S x S, `val_batch` above); Darknet's letter_box=1 and the later YOLO code bases do.
+
+LETTERBOX_FILL = 114
+LETTERBOX_MODES = ('square', 'rect')
+
+
+def letterbox_mode(value):
+    """None / 'off' -> None; 'square' | 'rect' -> itself; anything else: ValueError."""
+    if value is None or value == 'off':
+        return None
+    if value not in LETTERBOX_MODES:
+        raise ValueError("letterbox must be None, 'square' or 'rect', got %r" % (value,))
+    return value
+
+
+def letterbox_geometry(h, w, S):
+    """(nh, nw): the size an h x w image is resized to so that its longer side becomes S."""
+    h, w, S = int(h), int(w), int(S)
+    if h < 1 or w < 1 or S < 1:
+        raise ValueError('letterbox_geometry needs positive sizes, got %r' % ((h, w, S),))
+    r = S / max(h, w)
+    nh = min(S, max(1, int(np.floor(h * r + 0.5))))
+    nw = min(S, max(1, int(np.floor(w * r + 0.5))))
+    return nh, nw
+
+
+def letterbox_canvas(sizes, S, mode='rect', G=32):
+    """(Hc, Wc) of the canvas that holds a batch of resized (nh, nw) images: (S, S) for 'square'; for 'rect' the largest nh
+    and nw, each rounded up to a multiple of G (the model's largest stride).  S must be a multiple of G."""
+    S, G = int(S), int(G)
+    if mode not in LETTERBOX_MODES:
+        raise ValueError("letterbox mode must be 'square' or 'rect', got %r" % (mode,))
+    if G < 1 or S % G != 0:
+        raise ValueError('the input size %d is not a multiple of the largest stride %d' % (S, G))
+    if mode == 'square':
+        return S, S
+    sizes = list(sizes)
+    if not sizes:
+        raise ValueError('letterbox_canvas needs at least one image')
+    return -(-max(nh for nh, _ in sizes) // G) * G, -(-max(nw for _, nw in sizes) // G) * G
+
+
+def letterbox_offsets(nh, nw, Hc, Wc):
+    """(top, left) of an nh x nw image centred on an Hc x Wc canvas."""
+    return (Hc - nh) // 2, (Wc - nw) // 2
+
+
+def letterbox_batch(imgs, img_size, mode='rect', stride=32, fill=LETTERBOX_FILL, device=None, out=None, swap_rb=True):
+    """List of uint8 HWC BGR images of any sizes (numpy arrays or tensors on any device) -> ([B, 3, Hc, Wc] fp32 batch on the
+    GPU, infos) with infos[b] = [h, w, nh, nw, top, left].  One descriptor table goes from pinned memory to the device and ONE
+    launch (csrc/preprocess.hip) resizes every image with cv2.resize's 8-bit INTER_LINEAR arithmetic and writes the padding
+    around it; nothing waits for the device.  out: the batch to write into (any strides; its shape fixes the canvas)."""
+    S, B = int(img_size), len(imgs)
+    assert B >= 1
+    if out is not None:
+        device = out.device
+    device = device or torch.device('cuda', torch.cuda.current_device())
+    srcs = [_as_device_u8(im, device) for im in imgs]
+    geo = [letterbox_geometry(t.shape[0], t.shape[1], S) for t in srcs]
+    Hc, Wc = letterbox_canvas(geo, S, mode, stride)
+    if out is None:
+        out = torch.empty((B, 3, Hc, Wc), dtype=torch.float32, device=device)
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (B, 3, Hc, Wc)
+    host = torch.empty(B * ctypes.sizeof(LetterboxSrc), dtype=torch.uint8).pin_memory()
+    view = host.numpy()
+    table = (LetterboxSrc * B).from_buffer(view, 0)
+    infos = []
+    for r, t, (nh, nw) in zip(table, srcs, geo):
+        top, left = letterbox_offsets(nh, nw, Hc, Wc)
+        r.src, r.h, r.w, r.pitch, r.swap_rb = t.data_ptr(), int(t.shape[0]), int(t.shape[1]), int(t.stride(0)), 1 if swap_rb else 0
+        r.nh, r.nw, r.top, r.left, r.reserved = nh, nw, top, left, 0
+        infos.append([int(t.shape[0]), int(t.shape[1]), nh, nw, top, left])
+    del table, view
+    with torch.cuda.device(device):
+        dev = torch.empty(host.numel(), dtype=torch.uint8, device=device)
+        dev.copy_(host, non_blocking=True)
+        check(lib().y4_letterbox_batch_u8_f32(dev.data_ptr(), host.data_ptr(), B, out.data_ptr(), out.stride(0), out.stride(1),
+                                              out.stride(2), out.stride(3), Hc, Wc, int(fill), _stream()),
+              'y4_letterbox_batch_u8_f32')
+    return out, infos
+
+
+def letterbox_labels(boxes_xywh_cls, info):
+    """[K, 5] (x, y, w, h, cls) in source pixels -> (x1, y1, x2, y2, cls) on the letterboxed canvas, float64."""
+    h, w, nh, nw, top, left = info[:6]
+    b = np.array(boxes_xywh_cls, dtype=np.float64).reshape(-1, 5)
+    b[:, 2] += b[:, 0]
+    b[:, 3] += b[:, 1]
+    b[:, [0, 2]] = b[:, [0, 2]] * nw / w + left
+    b[:, [1, 3]] = b[:, [1, 3]] * nh / h + top
+    return b
 
 
 # ------------------------------------------------------------------------------------------------ training: parameters

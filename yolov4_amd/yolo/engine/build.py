@@ -125,7 +125,9 @@ def validate(val_loader, model, conf_threshold, nms_threshold, device=None, eval
     evaluator: the COCOeval protocol on the device.  Unlike the reference the loader may hand batches larger
     than 1: target['img_info'] is then a list of per-image [h, w, S, S, id, ...] rows.  `nms_options` (an NMSOptions, or a
     dict of postprocess_nms's keywords) selects DIoU- / Soft- / class-agnostic NMS and the per-image cap; None is the
-    reference's postprocess."""
+    reference's postprocess.  A loader that letterboxes its input (COCOBatchLoader(letterbox=...)) adds target['pad'], B rows
+    of (top, left), and img_info rows [h, w, nh, nw, id, ...]: boxes then go back through letterbox2xywh, clipped to the
+    image; without the key nothing changes."""
     if nms_options is not None and not isinstance(nms_options, dict):
         nms_options = nms_options.kwargs()
     model.eval()
@@ -134,6 +136,9 @@ def validate(val_loader, model, conf_threshold, nms_threshold, device=None, eval
     for img, target in val_loader:
         assert isinstance(target, dict)
         infos = _img_infos(target['img_info'], img.shape[0])
+        pads = target.get('pad')                       # letterboxed input: B rows of (top, left); absent: stretched
+        if pads is not None:
+            pads = [[float(v) for v in (p.tolist() if hasattr(p, 'tolist') else p)] for p in pads]
         with trace.range('y4.eval_forward'):
             outputs = model(img.to(device) if device is not None else img)                        # :133
         with trace.range('y4.postprocess'):
@@ -141,10 +146,12 @@ def validate(val_loader, model, conf_threshold, nms_threshold, device=None, eval
                 outputs = postprocess(outputs, num_classes, conf_threshold, nms_threshold)        # :137
             else:
                 outputs = postprocess_nms(outputs, num_classes, conf_threshold, nms_threshold, **nms_options)
-        for det, info in zip(outputs, infos):
+        for k, (det, info) in enumerate(zip(outputs, infos)):
             id_ = int(info[-2])
             ids.append(id_)
             kw = {'class_ids': class_ids} if class_ids is not None else {}
+            if pads is not None:
+                kw['pad'] = pads[k]
             data_list.extend(detections_to_coco(det, info[:4], id_, **kw))                        # :144-164
     validate.records = data_list
     if evaluator is not None and data_list:

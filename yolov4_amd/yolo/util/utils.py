@@ -238,14 +238,47 @@ def yolobox2yxyx(box, info_img):
     return [y1 * src_h / dst_h, x1 * src_w / dst_w, y2 * src_h / dst_h, x2 * src_w / dst_w]
 
 
-def detections_to_coco(detections, img_info, image_id, class_ids=COCO_CLASS_IDS):
+def _clip(v, hi):
+    """v limited to [0, hi]; Python floats or float64 arrays (a NaN stays a NaN)"""
+    return np.clip(v, 0.0, float(hi)) if isinstance(v, np.ndarray) else min(max(v, 0.0), float(hi))
+
+
+def letterbox2yxyx(box, info):
+    """(y1, x1, y2, x2) in the pixels of a letterboxed network input -> [y1, x1, y2, x2] in source-image pixels, clipped to
+    the image.  `info` = (h, w, nh, nw, top, left): the source's size, the size it was resized to and where that lies in
+    the canvas (`letterbox_batch`).  Double arithmetic, multiply then divide, as yolobox2yxyx."""
+    h, w, nh, nw, top, left = info[:6]
+    y1, x1, y2, x2 = box
+    return [_clip((y1 - top) * h / nh, h), _clip((x1 - left) * w / nw, w),
+            _clip((y2 - top) * h / nh, h), _clip((x2 - left) * w / nw, w)]
+
+
+def letterbox2xywh(box, info):
+    """(y1, x1, y2, x2) in the pixels of a letterboxed network input -> [x1, y1, w, h] in source-image pixels: the corners
+    of letterbox2yxyx (clipped to the image), then their differences."""
+    y1, x1, y2, x2 = letterbox2yxyx(box, info)
+    return [x1, y1, x2 - x1, y2 - y1]
+
+
+def detections_to_coco(detections, img_info, image_id, class_ids=COCO_CLASS_IDS, pad=None):
     """One image's postprocess() result [n,7] (or None) -> list of COCO result dicts, as validate() builds
     them (yolo/engine/build.py:144-164).  The reference converts every fp32 number to a Python float and
-    does the arithmetic in double precision; one device->host copy and the same double arithmetic here."""
+    does the arithmetic in double precision; one device->host copy and the same double arithmetic here.
+    pad = (top, left): the input was letterboxed, img_info[:4] = (h, w, nh, nw), and boxes go through letterbox2xywh
+    (clipped to the image); None is the reference's stretch arithmetic, without a clip."""
     if detections is None:
         return []
     d = detections.detach().cpu().numpy().astype(np.float64)
     out = []
+    if pad is not None:
+        info = [float(v) for v in img_info[:4]] + [float(pad[0]), float(pad[1])]
+        for r in d:
+            out.append({'image_id': image_id,
+                        'category_id': class_ids[int(r[6])],
+                        'bbox': letterbox2xywh((float(r[1]), float(r[0]), float(r[3]), float(r[2])), info),
+                        'score': float(r[4] * r[5]),
+                        'segmentation': []})
+        return out
     for r in d:
         out.append({'image_id': image_id,
                     'category_id': class_ids[int(r[6])],
