@@ -340,6 +340,25 @@ int y4_bn_act_bwd_f32(const float* dz, int lddz, const float* y, int ldy,
                          bit 1 (conv mode 2): dy leaves as plain bf16 in the first half of each fp32-sized row, as
                          y4_bn_act_fwd_f32 z_planes == 3 (lddy == C, C % 32 == 0, f16_planes NULL) */,
                       void* stream);
+/* The backward of conv 1x1 / stride 1 -> BatchNorm (batch statistics) -> activation in one call, conv mode 3, for the HBM-bound
+ * layers on large maps ((Cout, Cin) in {(64, 64), (32, 64), (64, 128)}): y4_bn_act_bwd_f32 with the plane bound, then
+ * y4_conv2d_dgrad_f32 and y4_conv2d_wgrad_f32 on its dy -- but dy is formed in registers by ONE kernel that reads dz, y, x
+ * (+ res) and writes dx and the split-K slabs of dW; it is never stored (csrc/conv1x1_bwd_fused.hip).  dy is split under the
+ * bound of max|dy| the reduce pass derives (bounds[5], as f16_planes above), not under a measured maximum.  Two-stage
+ * fixed-order reductions throughout: deterministic.  Any other shape, frozen statistics, another conv mode or a pointer / pitch
+ * that is not 16-byte aligned returns Y4_ERR_SHAPE before anything is launched or written. */
+size_t y4_conv1x1_bn_act_bwd_fused_workspace(long long M, int Cin, int Cout);
+int y4_conv1x1_bn_act_bwd_fused_f32(const float* dz, int lddz, const float* y, int ldy,
+                                    const float* mean, const float* invstd, const float* gamma, const float* beta, int act,
+                                    float* dgamma, float* dbeta, long long M /* B*H*W */, int Cin, int Cout,
+                                    const float* x, int ldx, const unsigned* x_amax /* nullable: one extra pass over x */,
+                                    const float* w /* [Cout][Cin]; may be NULL with w_prepared */,
+                                    const void* w_prepared /* nullable: the transposed split filter as the forward call left it in
+                                       its dgrad_filter buffer (y4_conv2d_fwd_bnstats_f32), maximum word included */,
+                                    float* dx, int lddx, const float* res /* nullable [M][Cin]: added to dx */, int ldr,
+                                    float* dw /* [Cout][Cin] */, void* workspace, size_t workspace_bytes,
+                                    unsigned* bounds /* 8 zeroed device words; [5] receives the bound of max|dy| */,
+                                    int frozen_stats /* must be 0 */, void* stream);
 /* dbias[c] = sum_m dy[m,c]  (bias=True head convs, yolov4.py:237,243,249): two fixed-order stages, no atomics
  * (deterministic).  workspace: y4_bias_grad_workspace(M, C) bytes */
 size_t y4_bias_grad_workspace(long long M, int C);

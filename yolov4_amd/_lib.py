@@ -71,6 +71,8 @@ PROTOTYPES = {
     'y4_bn_act_fwd_f32': (I, [P, I, P, P, P, P, I, P, I, P, I, L, I, P, I, P, P, P]),
     'y4_bn_planes_bound_f32': (I, [P, P, I, L, P, P, P]),
     'y4_bn_act_bwd_f32': (I, [P, I, P, I, P, P, P, P, I, P, I, P, P, L, I, P, Z, P, P, P, I, P]),
+    'y4_conv1x1_bn_act_bwd_fused_workspace': (Z, [L, I, I]),
+    'y4_conv1x1_bn_act_bwd_fused_f32': (I, [P, I, P, I, P, P, P, P, I, P, P, L, I, I, P, I, P, P, P, P, I, P, I, P, P, Z, P, I, P]),
     'y4_bias_grad_workspace': (Z, [L, I]),
     'y4_bias_grad_f32': (I, [P, I, L, I, P, P, Z, P]),
     'y4_bn_fold_f32': (I, [P, P, P, P, F, P, P, I, P]),

@@ -176,6 +176,11 @@ namespace y4 {
 // head of `workspace` (y4_bn_finalize_workspace(C) bytes), fixed order
 int bn_bwd_fold_finalize(const float* part, long long nparts, long long M, int C, void* workspace, float* dgamma, float* dbeta,
                          const float* gamma, const float* invstd, hipStream_t st);
+// pointwise.hip: reduce (with the bound words [0..4] of the 6 zeroed words `bounds`), fold and finalize of the BatchNorm backward
+// over dz, y -> dbeta, dgamma and the fp64 words acc[2C] at the head of `workspace` (y4_bn_workspace(M, C) bytes)
+int bn_bwd_reduce_finalize_bounds(const float* dz, int lddz, const float* y, int ldy, const float* mean, const float* invstd,
+                                  const float* gamma, const float* beta, int act, long long M, int C, void* workspace,
+                                  float* dgamma, float* dbeta, unsigned* bounds, hipStream_t st);
 // conv_igemm.hip: per-wave slabs [nslabs][32 n][32 j] -> dw[Cout][27] through part[64][1024] doubles, fixed order
 int stem_wgrad_fold(const float* slabs, int nslabs, double* part, float* dw, int Cout, hipStream_t st);
 }  // namespace y4

@@ -1048,6 +1048,30 @@ int y4_bn_act_fwd_f32(const float* y, int ldy, const float* mean, const float* i
     return Y4_OK;
 }
 
+// backward pass 1 and the first fold: per-block rows of (sum g, sum g xhat) into `part`, folded into bacc[*nb][2C]; with
+// `bounds` the reduce pass also leaves max|g| and max|xhat| in words [0], [1]
+static int bn_bwd_reduce_fold(const float* dz, int lddz, const float* y, int ldy, const float* mean, const float* invstd,
+                              const float* gamma, const float* beta, int act, long long M, int C, float* part, double* bacc, int* nb,
+                              unsigned* bounds, int ybf, hipStream_t st) {
+    const RowMap rm = row_map(C);
+    const int nrows = stat_rows(M, rm.rpb);
+    const long long rblocks = bn_blocks(M, C);
+    const bool nt = bn_loads_nt(M, C);
+#define Y4_BN_RED(BND_, YBF_)                                                                                                    \
+    if (nt) Y4_BN_RED_(BND_, YBF_, true); else Y4_BN_RED_(BND_, YBF_, false)
+#define Y4_BN_RED_(BND_, YBF_, NT_)                                                                                              \
+    hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<A_, BND_, YBF_, NT_>), dim3((unsigned)rblocks), dim3(PW_THREADS), 0, st, dz,      \
+                       (long long)lddz, y, (long long)ldy, mean, invstd, gamma, beta, M, C, rm.tpr, rm.rpb, nrows, part, bounds)
+    if (bounds && ybf) return Y4_ERR_SHAPE;                // (bf16 conv results exist only in the bf16 plane mode: no bounds there)
+    if (bounds) { Y4_ACT_SWITCH(act, Y4_BN_RED(true, false)); }
+    else if (ybf) { Y4_ACT_SWITCH(act, Y4_BN_RED(false, true)); }
+    else { Y4_ACT_SWITCH(act, Y4_BN_RED(false, false)); }
+#undef Y4_BN_RED
+#undef Y4_BN_RED_
+    Y4_CHECK_LAUNCH();
+    return fold_partials(part, rblocks, C, bacc, nb, st);
+}
+
 static int bn_act_bwd_impl(const float* dz, int lddz, const float* y, int ldy,
                            const float* mean, const float* invstd, const float* gamma, const float* beta,
                            int act, float* dy, int lddy, float* dgamma, float* dbeta,
@@ -1065,25 +1089,10 @@ static int bn_act_bwd_impl(const float* dz, int lddz, const float* y, int ldy,
     double* bacc = acc + 2 * C;
     float* part = reinterpret_cast<float*>(acc + (size_t)(1 + FOLD_BLOCKS) * 2 * C);
     const RowMap rm = row_map(C);
-    const int nrows = stat_rows(M, rm.rpb);
-    const long long rblocks = bn_blocks(M, C);
     int nb = 0;
     const bool nt = bn_loads_nt(M, C);
     {
-#define Y4_BN_RED(BND_, YBF_)                                                                                                    \
-        if (nt) Y4_BN_RED_(BND_, YBF_, true); else Y4_BN_RED_(BND_, YBF_, false)
-#define Y4_BN_RED_(BND_, YBF_, NT_)                                                                                              \
-        hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<A_, BND_, YBF_, NT_>), dim3((unsigned)rblocks), dim3(PW_THREADS), 0, st, dz,  \
-                           (long long)lddz, y, (long long)ldy, mean, invstd, gamma, beta, M, C, rm.tpr, rm.rpb, nrows, part,       \
-                           f16_planes)
-        if (f16_planes && ybf) return Y4_ERR_SHAPE;        // (bf16 conv results exist only in the bf16 plane mode: no bounds there)
-        if (f16_planes) { Y4_ACT_SWITCH(act, Y4_BN_RED(true, false)); }
-        else if (ybf) { Y4_ACT_SWITCH(act, Y4_BN_RED(false, true)); }
-        else { Y4_ACT_SWITCH(act, Y4_BN_RED(false, false)); }
-#undef Y4_BN_RED
-#undef Y4_BN_RED_
-        Y4_CHECK_LAUNCH();
-        const int rc = fold_partials(part, rblocks, C, bacc, &nb, st);
+        const int rc = bn_bwd_reduce_fold(dz, lddz, y, ldy, mean, invstd, gamma, beta, act, M, C, part, bacc, &nb, f16_planes, ybf, st);
         if (rc != Y4_OK) return rc;
     }
     if (f16_planes && ((!planes_twin && lddy != C) || (C & 31))) return Y4_ERR_SHAPE;       // planes: dense rows, whole 32-channel K-tiles
@@ -1267,6 +1276,23 @@ int bn_bwd_fold_finalize(const float* part, long long nparts, long long M, int C
     if (rc != Y4_OK) return rc;
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, st, bacc, nb, C, acc, dgamma, dbeta, gamma,
                        invstd, 1.0 / (double)M, static_cast<unsigned*>(nullptr));
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+// all three stages for a caller that applies the result itself (conv1x1_bwd_fused.hip): the reduce pass with the bound words,
+// fold and finalize exactly as bn_act_bwd_impl launches them for a plane layer.  workspace: y4_bn_workspace(M, C) bytes, whose
+// head acc[2C] holds (sum g, sum g xhat) in fp64 afterwards; bounds: 6 zeroed words, [0..4] filled
+int bn_bwd_reduce_finalize_bounds(const float* dz, int lddz, const float* y, int ldy, const float* mean, const float* invstd,
+                                  const float* gamma, const float* beta, int act, long long M, int C, void* workspace,
+                                  float* dgamma, float* dbeta, unsigned* bounds, hipStream_t st) {
+    double* acc = static_cast<double*>(workspace);
+    double* bacc = acc + 2 * C;
+    float* part = reinterpret_cast<float*>(acc + (size_t)(1 + FOLD_BLOCKS) * 2 * C);
+    int nb = 0;
+    const int rc = bn_bwd_reduce_fold(dz, lddz, y, ldy, mean, invstd, gamma, beta, act, M, C, part, bacc, &nb, bounds, 0, st);
+    if (rc != Y4_OK) return rc;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 31) / 32), dim3(256), 0, st, bacc, nb, C, acc, dgamma, dbeta, gamma,
+                       invstd, 1.0 / (double)M, bounds);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }

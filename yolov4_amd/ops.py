@@ -805,6 +805,55 @@ def bn_act_bwd_raw(dz, y, mean, invstd, gamma, beta, act, dgamma_out=None, dbeta
     return dy, dgamma, dbeta
 
 
+# The HBM-bound 1x1 layers on the large maps: BatchNorm backward apply, dgrad and wgrad as ONE kernel that keeps dy in
+# registers (csrc/conv1x1_bwd_fused.hip).  Y4_FUSED_1X1_BWD=0 turns the route off (the A/B lever: the three kernels of before).
+FUSED_1X1 = {'on': os.environ.get('Y4_FUSED_1X1_BWD', '1') != '0'}
+FUSED_1X1_SHAPES = ((64, 64), (32, 64), (64, 128))        # (Cout, Cin)
+FUSED_1X1_MIN_ROWS = 131072                               # the streaming 1x1 kernels' own threshold
+
+
+def fused_1x1_bwd_shape(M, Cin, Cout, k, s):
+    return k == 1 and s == 1 and (Cout, Cin) in FUSED_1X1_SHAPES and M >= FUSED_1X1_MIN_ROWS
+
+
+def conv1x1_bn_act_bwd_fused_raw(dz, y, x, w, mean, invstd, gamma, beta, act, x_amax=None, residual=None, prepared=None,
+                                 dgamma_out=None, dbeta_out=None, dw_out=None):
+    """Backward of conv 1x1 / s1 -> BatchNorm (batch statistics) -> act wrt x, w, gamma, beta: (dx, dw, dgamma, dbeta).
+    residual: added to dx (a parked skip gradient); prepared: the forward call's transposed filter planes; the *_out
+    destinations (gradient slots of a flat DDP bucket) are written in place when they qualify."""
+    L = lib()
+    B, Cin, H, W = x.shape
+    Cout = w.shape[0]
+    M = B * H * W
+    dz, lddz = as_nhwc(dz)
+    y, ldy = as_nhwc(y)
+    x, ldx = as_nhwc(x)
+    ldr = 0
+    if residual is not None:
+        residual, ldr = as_nhwc(residual)
+    dx = empty_nhwc(B, Cin, H, W, x.device)
+
+    def slot(t):
+        ok = t is not None and t.dtype == torch.float32 and tuple(t.shape) == (Cout,) and t.is_contiguous() and t.is_cuda
+        return t if ok else torch.empty(Cout, device=x.device, dtype=torch.float32)
+    dgamma, dbeta = slot(dgamma_out), slot(dbeta_out)
+    if dw_out is not None and tuple(dw_out.shape) == tuple(w.shape) and _is_krsc_dense(dw_out) and dw_out.data_ptr() % 16 == 0:
+        dw = dw_out
+        WGRAD_STATS['in_place'] += 1
+    else:
+        WGRAD_STATS['temporary'] += 1
+        dw = krsc(torch.empty(tuple(w.shape), device=x.device, dtype=torch.float32).contiguous(memory_format=CL))
+    cell = planes_cell(x.device, 8)
+    nbytes = L.y4_conv1x1_bn_act_bwd_fused_workspace(M, Cin, Cout)
+    ws = _ws(nbytes, x.device)
+    check(L.y4_conv1x1_bn_act_bwd_fused_f32(_ptr(dz), lddz, _ptr(y), ldy, _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
+                                            ACT_IDS[act], _ptr(dgamma), _ptr(dbeta), M, Cin, Cout, _ptr(x), ldx, _ptr(x_amax),
+                                            None if prepared is not None else _ptr(krsc(w)), _ptr(prepared), _ptr(dx), nhwc_pitch(dx),
+                                            _ptr(residual), ldr, _ptr(dw), _ptr(ws), nbytes, _ptr(cell), 0, _stream()),
+          'conv1x1_bn_act_bwd_fused')
+    return dx, dw, dgamma, dbeta
+
+
 def bias_grad_raw(dy):
     L = lib()
     B, C, H, W = dy.shape
@@ -1135,6 +1184,12 @@ class ConvBNActFn(torch.autograd.Function):
             sink = (gp is not None and bp is not None and getattr(gp, '_y4_grad_fresh', False)
                     and getattr(bp, '_y4_grad_fresh', False) and gp.grad is not None and bp.grad is not None
                     and ctx.needs_input_grad[3] and ctx.needs_input_grad[4])
+            # the HBM-bound 1x1 layers of stage 1 / 2: apply, dgrad and wgrad in one kernel, dy never stored
+            if (ctx.mode == 'bn_train' and FUSED_1X1['on'] and f16 and not x_planes and planes_mode() == 'f16x2'
+                    and not getattr(ctx, 'y_bf16', False) and not _ASYNC['on'] and x_amax is not None
+                    and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
+                    and fused_1x1_bwd_shape(dz.shape[0] * dz.shape[2] * dz.shape[3], ctx.x_shape[1], weight.shape[0], k, s)):
+                return ConvBNActFn._backward_fused_1x1(ctx, dz, x_amax, sink)
             # a layer whose input came pre-split runs dgrad and wgrad on the plane kernels: dy leaves the BatchNorm
             # backward sweep already split, scaled by a bound of max|dy| the reduce pass derives (word [5] of the cell)
             bfp = x_planes and planes_mode() == 'bf16'       # conv mode 2: dy leaves as plain bf16, no scale word
@@ -1235,6 +1290,45 @@ class ConvBNActFn(torch.autograd.Function):
             put['dres'] = dres                      # consumed by the unit's 1x1 conv (dres_take); autograd sees no gradient
             dres = None
         return dx, dw, dbias, dgamma, dbeta, dres, None
+
+    @staticmethod
+    def _backward_fused_1x1(ctx, dz, x_amax, sink):
+        """backward() of a 'bn_train' layer on the fused 1x1 route (conv1x1_bn_act_bwd_fused_raw): the same hand-offs as the
+        unfused sequence -- parked skip gradient in, dx parked for the fork's other branch, DDP gradient slots written in place."""
+        cfg = ctx.cfg
+        x, weight, y, mean, invstd, gamma, beta = ctx.saved_tensors
+        gp, bp, param = cfg.get('gamma_param'), cfg.get('beta_param'), cfg.get('weight_param')
+        take = cfg.get('dres_take')
+        skip_grad = take.pop('dres', None) if take is not None else None
+        if take is not None and skip_grad is None:
+            take['taker_done'] = True
+        wsink = param is not None and getattr(param, '_y4_grad_fresh', False) and param.grad is not None
+        dx, dw, dgamma, dbeta = conv1x1_bn_act_bwd_fused_raw(
+            dz, y, x, weight, mean, invstd, gamma, beta, cfg['act'], x_amax=x_amax, residual=skip_grad,
+            prepared=getattr(ctx, 'dgrad_filter', None), dgamma_out=gp.grad if sink else None, dbeta_out=bp.grad if sink else None,
+            dw_out=param.grad if wsink else None)
+        ctx.dgrad_filter = None
+        if sink and dgamma is gp.grad and dbeta is bp.grad:
+            gp._y4_grad_fresh = bp._y4_grad_fresh = False
+            gp._y4_grad_ready()
+            bp._y4_grad_ready()
+            dgamma = dbeta = None
+        fbox = cfg.get('dx_put')
+        if fbox is not None and not fbox.get('taker_done'):
+            fbox['dres'] = dx
+            dx = None
+        if wsink:
+            param._y4_grad_fresh = False
+            if dw is not param.grad:
+                param.grad.add_(dw)
+            param._y4_grad_ready()
+            dw = None
+        dres = dz if ctx.has_res else None
+        put = cfg.get('dres_put')
+        if dres is not None and put is not None:
+            put['dres'] = dres
+            dres = None
+        return dx, dw, None, dgamma, dbeta, dres, None
 
 
 class Fork2Fn(torch.autograd.Function):
