@@ -637,6 +637,28 @@ size_t y4_post_topk_workspace(long long total_candidates, int n_segments);
 int y4_post_topk_compact_f32(const float* det_rows, const int* seg_offsets, const int* kept, int B, int segs_per_image,
                              int max_det, long long total_candidates, float* out_rows, int* out_offsets,
                              int* img_offsets, void* workspace, size_t workspace_bytes, void* stream);
+/* ---------------------------------------------------------------- weighted box fusion
+ * Solovyev et al.'s merge rule in place of suppression, on the same stages: y4_post_count_ex_f32, y4_post_scan_i32 before it,
+ * y4_post_compact_f32 or y4_post_topk_compact_f32 behind it, the contract of y4_post_nms_ex_f32 (segments, keys, capacity).
+ * One 256-thread block per segment walks its candidates in key order j = 0 .. n-1.  Candidate: score s_j = obj * cls (one
+ * fp32 product), xyxy box x_j.  Cluster t: fused box F_t, sums Sx1 Sy1 Sx2 Sy2 S, count n_t, class.  For candidate j
+ *   m_t = the Y4_NMS_IOU measure above with a = x_j and o = F_t (areas from the boxes) for every cluster;
+ *   it matches t when m_t > iou_thre (strict; a NaN never matches); the cluster with the largest m_t takes it (ties: lowest t):
+ *     Sx1 = Sx1 + s_j * x1_j (one product, one add; the other corners likewise), S = S + s_j, n_t += 1,
+ *     F_t = (Sx1 / S, Sy1 / S, Sx2 / S, Sy2 / S);
+ *   without a match it opens a cluster: sums from the same products, S = s_j, n_t = 1, F = x_j itself, class = its class
+ *   (agnostic = 1: clusters of a whole image, whatever the classes of their later members).
+ * Rows, in creation order: (F.x1, F.y1, F.x2, F.y2, 1.0, score, class) with mean = S / float(n_t),
+ * f = float(min(n_t, n_views)) / float(n_views), score = mean * f: row[4] * row[5] is the fused score.
+ * Scores do not decay, so a segment takes n sequential steps (an image-sized agnostic segment is slow); max_det acts only
+ * through y4_post_topk_compact_f32.  Cluster state lives in LDS up to 1024 candidates per segment, in the workspace above.
+ * Errors before any launch: NULL pointer Y4_ERR_NULL; n_views < 1, agnostic outside {0, 1}, an iou_thre that is not >= 0
+ * (NaN included) or a bad shape Y4_ERR_SHAPE; workspace too small Y4_ERR_WORKSPACE. */
+size_t y4_post_wbf_workspace(long long total_candidates, int n_segments);
+int y4_post_wbf_f32(const float* prediction, int B, long long N, int n_classes, float conf_thre, float iou_thre, int agnostic,
+                    int n_views, const int* seg_offsets /* [segments+1] device */, long long total_candidates,
+                    float* det_rows /* [total,7] */, int* kept /* [segments] */, void* workspace, size_t workspace_bytes,
+                    void* stream);
 /* plain greedy NMS on one list (nms(), utils.py:32): boxes [R,4] xyxy, order given by
  * score desc / index asc; writes keep flags in sorted order and the sorted index list. */
 size_t y4_nms_workspace(long long R);
@@ -1182,6 +1204,29 @@ int y4_rcrop_randaug_u8_f32(const y4_rcrop_job* jobs_dev, const y4_rcrop_job* jo
 int y4_anchor_assign_f32(const float* wh, int N, const float* anchors, int A, float iou_thresh, unsigned char* assign,
                          float* best_iou, long long* acc, void* stream);
 int y4_anchor_fitness_f32(const float* wh, int N, const float* cand, int G, int A, float thr, long long* out, void* stream);
+
+/* ---- test-time augmentation (csrc/tta.hip) -----------------------------------------------------
+ * y4_tta_view_f32: one rescaled, optionally mirrored view out [B][C][Hv][Wv] of an fp32 batch in [B][C][H][W] in one launch;
+ *   both tensors by their strides in elements (b, c, y, x).  With xs = flip ? Wv - 1 - x : x:
+ *     y >= ch or xs >= cw: out(b, c, y, x) = fill (the padding up to the stride multiple);
+ *     else a bilinear sample with half-pixel centres and no antialiasing, each step one fp32 operation in this order:
+ *       sy = (float(y) + 0.5f) * ry - 0.5f, clamped to [0, H - 1]; y0 = floorf(sy), fy = sy - y0, y1 = min(y0 + 1, H - 1);
+ *       the same for sx from xs with rx; with a, b = in(y0, x0), in(y0, x1) and c, d = in(y1, x0), in(y1, x1):
+ *       top = a + (b - a) * fx, bot = c + (d - c) * fx, out = top + (bot - top) * fy.
+ *   The host chooses ch = max(1, int(H * r)), Hv = ch rounded up to the model's largest stride, ry = float(H) / float(ch)
+ *   (and the same in x).  Errors before any launch: NULL Y4_ERR_NULL; a size outside [1, 65535], ch > Hv, cw > Wv, flip
+ *   outside {0, 1} or a ratio that is not > 0 Y4_ERR_SHAPE.
+ * y4_tta_merge_f32: one view's eval prediction pred [B][N][n_ch] (centre-xywh boxes in the view's pixels) into rows
+ *   [row_off, row_off + N) of every image of out [B][n_total][n_ch], the boxes mapped to base-canvas pixels:
+ *     cx' = (flip ? view_w - cx : cx) * inv_sx, cy' = cy * inv_sy, w' = w * inv_sx, h' = h * inv_sy (one fp32 operation per
+ *   step); columns 4.. are copied.  With flip = 0 and both factors 1.0 the box columns are copied too, not multiplied.
+ *   The host computes inv_sx = float(W) / float(cw).  Errors before any launch: NULL Y4_ERR_NULL; row_off + N > n_total,
+ *   n_ch < 5, N * n_ch >= 2^31, B outside [1, 65535], flip outside {0, 1} or a non-positive size Y4_ERR_SHAPE. */
+int y4_tta_view_f32(const float* in, int B, int C, int H, int W, long long in_sb, long long in_sc, long long in_sy,
+                    long long in_sx, float* out, int Hv, int Wv, long long out_sb, long long out_sc, long long out_sy,
+                    long long out_sx, int ch, int cw, float ry, float rx, int flip, float fill, void* stream);
+int y4_tta_merge_f32(const float* pred, int B, long long N, int n_ch, float* out, long long n_total, long long row_off,
+                     float view_w, int flip, float inv_sx, float inv_sy, void* stream);
 
 #ifdef __cplusplus
 }

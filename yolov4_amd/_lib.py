@@ -119,6 +119,8 @@ PROTOTYPES = {
     'y4_post_nms_ex_f32': (I, [P, I, L, I, F, F, P, P, L, P, P, P, Z, P]),
     'y4_post_topk_workspace': (Z, [L, I]),
     'y4_post_topk_compact_f32': (I, [P, P, P, I, I, I, L, P, P, P, P, Z, P]),
+    'y4_post_wbf_workspace': (Z, [L, I]),
+    'y4_post_wbf_f32': (I, [P, I, L, I, F, F, I, I, P, L, P, P, P, Z, P]),
     'y4_nms_workspace': (Z, [L]),
     'y4_nms_f32': (I, [P, P, L, F, I, P, P, P, Z, P]),
     'y4_bboxes_iou_f32': (I, [P, L, P, L, I, P, P]),
@@ -165,6 +167,8 @@ PROTOTYPES = {
     'y4_rcrop_randaug_u8_f32': (I, [P, P, I, I, P, P, P, L, L, L, L, P, Z, P, P, I, P, Z, P]),
     'y4_anchor_assign_f32': (I, [P, I, P, I, F, P, P, P, P]),
     'y4_anchor_fitness_f32': (I, [P, I, P, I, I, F, P, P]),
+    'y4_tta_view_f32': (I, [P, I, I, I, I, L, L, L, L, P, I, I, L, L, L, L, I, I, F, F, I, F, P]),
+    'y4_tta_merge_f32': (I, [P, I, L, I, P, L, L, F, I, F, F, P]),
 }
 
 ERR_FORMAT, ERR_UNSUPPORTED = 6, 7

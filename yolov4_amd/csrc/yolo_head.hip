@@ -1396,6 +1396,143 @@ __global__ __launch_bounds__(256) void post_soft_nms_kernel(const float* __restr
     if (threadIdx.x == 0) kept_out[seg] = kept;
 }
 
+// ---- Weighted box fusion (Solovyev et al.), one block per segment.  Candidates are walked in key order j = 0 .. n-1; cluster
+// t holds its fused box F_t, the score-weighted corner sums, the score sum S_t, its member count and its class.  Per
+// candidate: every thread measures it against the clusters t = tid, tid + 256, ... (a = the candidate, o = F_t, the 'iou'
+// sequence of nms_measure), keeps the best strict match (value descending, index ascending: any fold order gives the same
+// winner), 64 lanes fold by shuffles and the four waves through LDS (two buffers in turn: ONE barrier per candidate).  The
+// update is one thread's work: cluster t is only ever read and written by thread t % 256, so the next candidate's scan sees it
+// without a second barrier.  Scores do not decay: a segment always takes n steps, n read before the loop starts.
+// Candidates (box, score, class) are gathered once into the workspace and read one step ahead of their use.
+constexpr int WBF_LDS_CLUSTERS = 1024;                      // cluster state in LDS up to here (44 B each), else the workspace
+
+struct WbfState { float4* F; float4* sum; float* S; int* cnt; int* cls; };
+
+__device__ __forceinline__ int wbf_walk(int n, float thresh, const float4* cbox, const float* cs, const int* ccls,
+                                        const WbfState st, SoftRed& red) {
+    int T = 0;                                                  // uniform
+    float4 bx = cbox[0];
+    float s = cs[0];
+    int cl = ccls[0];
+    for (int j = 0; j < n; ++j) {
+        const float4 a = bx;
+        const float sa = s;
+        const int ca = cl;
+        if (j + 1 < n) { bx = cbox[j + 1]; s = cs[j + 1]; cl = ccls[j + 1]; }
+        const float area = (a.z - a.x) * (a.w - a.y);
+        float bv = 0.f;
+        int bj = -1;
+        for (int t = threadIdx.x; t < T; t += 256) {
+            const float4 o = st.F[t];
+            const float m = nms_measure<Y4_NMS_IOU>(a, area, o, (o.z - o.x) * (o.w - o.y));
+            if (m > thresh && (bj < 0 || m > bv)) { bv = m; bj = t; }      // NaN: no match; ascending t: the first of equals stays
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const float ov = __shfl_down(bv, off, 64);
+            const int oj = __shfl_down(bj, off, 64);
+            if (oj >= 0 && (bj < 0 || ov > bv || (ov == bv && oj < bj))) { bv = ov; bj = oj; }
+        }
+        const int buf = j & 1;
+        if ((threadIdx.x & 63) == 0) { red.v[buf][threadIdx.x >> 6] = bv; red.j[buf][threadIdx.x >> 6] = bj; }
+        __syncthreads();
+        bv = red.v[buf][0]; bj = red.j[buf][0];
+#pragma unroll
+        for (int q = 1; q < 4; ++q) {
+            const float ov = red.v[buf][q];
+            const int oj = red.j[buf][q];
+            if (oj >= 0 && (bj < 0 || ov > bv || (ov == bv && oj < bj))) { bv = ov; bj = oj; }
+        }
+        const int t = bj >= 0 ? bj : T;
+        if ((int)threadIdx.x == (t & 255)) {
+            const float px1 = sa * a.x, py1 = sa * a.y, px2 = sa * a.z, py2 = sa * a.w;
+            if (bj >= 0) {
+                float4 sm = st.sum[t];
+                sm.x = sm.x + px1; sm.y = sm.y + py1; sm.z = sm.z + px2; sm.w = sm.w + py2;
+                const float S = st.S[t] + sa;
+                st.sum[t] = sm;
+                st.S[t] = S;
+                st.cnt[t] = st.cnt[t] + 1;
+                st.F[t] = make_float4(sm.x / S, sm.y / S, sm.z / S, sm.w / S);
+            } else {
+                st.sum[t] = make_float4(px1, py1, px2, py2);
+                st.S[t] = sa;
+                st.cnt[t] = 1;
+                st.cls[t] = ca;
+                st.F[t] = a;
+            }
+        }
+        if (bj < 0) ++T;
+    }
+    return T;
+}
+
+// rows (F, 1, S / n * min(n, views) / views, class) in creation order; thread t % 256 reads what it wrote itself
+__device__ __forceinline__ void wbf_emit(int T, int n_views, const WbfState st, float* __restrict__ rows) {
+    const float fv = (float)n_views;
+    for (int t = threadIdx.x; t < T; t += 256) {
+        const float4 F = st.F[t];
+        const int cnt = st.cnt[t];
+        const float mean = st.S[t] / (float)cnt;
+        const float f = (float)min(cnt, n_views) / fv;
+        float* o = rows + (long long)t * 7;
+        o[0] = F.x; o[1] = F.y; o[2] = F.z; o[3] = F.w; o[4] = 1.f; o[5] = mean * f; o[6] = (float)st.cls[t];
+    }
+}
+
+template <bool AGN>
+__global__ __launch_bounds__(256) void post_wbf_kernel(const float* __restrict__ pred, long long N, int C, float thresh,
+                                                       int n_views, const int* __restrict__ seg_off,
+                                                       unsigned long long* __restrict__ keys, float4* cbox, float* cs,
+                                                       int* ccls, float4* gF, float4* gsum, float* gS, int* gcnt, int* gcls,
+                                                       float* __restrict__ det_rows, int* __restrict__ kept_out) {
+    // F 16 KiB | sums 16 KiB | S 4 KiB | count 4 KiB | class 4 KiB; the sort's key copy (16 KiB) uses the front before they do
+    __shared__ __attribute__((aligned(16))) unsigned char lds[WBF_LDS_CLUSTERS * 44];
+    __shared__ SoftRed red;
+    static_assert(WBF_LDS_CLUSTERS * 44 >= NMS_LDS_KEYS * 8, "the key copy must fit");
+    const int seg = blockIdx.x;
+    const int off = seg_off[seg];
+    const int n = seg_off[seg + 1] - off;
+    if (n == 0) { if (threadIdx.x == 0) kept_out[seg] = 0; return; }
+    const int b = AGN ? seg : seg / C, c = AGN ? 0 : seg - b * C;
+    const int n_ch = 5 + C;
+    unsigned long long* k = keys + off;
+    if (n <= NMS_LDS_KEYS) {
+        unsigned long long* skeys = reinterpret_cast<unsigned long long*>(lds);
+        for (int i = threadIdx.x; i < n; i += 256) skeys[i] = k[i];
+        __syncthreads();
+        block_bitonic_sort(skeys, n);
+        for (int i = threadIdx.x; i < n; i += 256) k[i] = skeys[i];
+        __syncthreads();
+    } else {
+        block_bitonic_sort(k, n);
+    }
+    const float* img = pred + (long long)b * N * n_ch;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const unsigned long long key = k[i];
+        const unsigned low = (unsigned)(key & 0xffffffffull);
+        const unsigned idx = AGN ? low / (unsigned)C : low;
+        const float* p = img + (long long)idx * n_ch;
+        cbox[off + i] = make_float4(p[0], p[1], p[2], p[3]);
+        cs[off + i] = key_score(key);
+        ccls[off + i] = AGN ? (int)(low - idx * (unsigned)C) : c;
+    }
+    __syncthreads();
+    int T;                                                      // (two calls: each inlines with its own address space)
+    if (n <= WBF_LDS_CLUSTERS) {
+        const WbfState st = {reinterpret_cast<float4*>(lds), reinterpret_cast<float4*>(lds + WBF_LDS_CLUSTERS * 16),
+                             reinterpret_cast<float*>(lds + WBF_LDS_CLUSTERS * 32),
+                             reinterpret_cast<int*>(lds + WBF_LDS_CLUSTERS * 36),
+                             reinterpret_cast<int*>(lds + WBF_LDS_CLUSTERS * 40)};
+        T = wbf_walk(n, thresh, cbox + off, cs + off, ccls + off, st, red);
+        wbf_emit(T, n_views, st, det_rows + (long long)off * 7);
+    } else {
+        const WbfState st = {gF + off, gsum + off, gS + off, gcnt + off, gcls + off};
+        T = wbf_walk(n, thresh, cbox + off, cs + off, ccls + off, st, red);
+        wbf_emit(T, n_views, st, det_rows + (long long)off * 7);
+    }
+    if (threadIdx.x == 0) kept_out[seg] = T;
+}
+
 __global__ __launch_bounds__(256) void nms_keys_kernel(const float* __restrict__ scores, long long R,
                                                        unsigned long long* __restrict__ keys) {
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < R; i += (long long)gridDim.x * blockDim.x)
@@ -1585,6 +1722,25 @@ static TopkWs topk_ws(long long total, int nseg) {
     w.total = o;
     return w;
 }
+// WBF: keys and cursors as PostWs; the gathered candidates; the cluster state of segments above WBF_LDS_CLUSTERS
+struct WbfWs { size_t keys, cursor, cbox, cs, ccls, F, sum, S, cnt, cls, total; };
+static WbfWs wbf_ws(long long total, int nseg) {
+    WbfWs w;
+    size_t o = 0;
+    const size_t t = (size_t)(total > 0 ? total : 1);
+    w.keys = o; o = al16(o + t * 8);
+    w.cursor = o; o = al16(o + (size_t)(nseg > 0 ? nseg : 1) * 4);
+    w.cbox = o; o = al16(o + t * 16);
+    w.cs = o; o = al16(o + t * 4);
+    w.ccls = o; o = al16(o + t * 4);
+    w.F = o; o = al16(o + t * 16);
+    w.sum = o; o = al16(o + t * 16);
+    w.S = o; o = al16(o + t * 4);
+    w.cnt = o; o = al16(o + t * 4);
+    w.cls = o; o = al16(o + t * 4);
+    w.total = o;
+    return w;
+}
 static bool nms_opts_ok(const y4_nms_opts* o) {
     return (o->metric == Y4_NMS_IOU || o->metric == Y4_NMS_DIOU) &&
            (o->soft == Y4_SOFT_NONE || o->soft == Y4_SOFT_LINEAR || o->soft == Y4_SOFT_GAUSSIAN) &&
@@ -1596,6 +1752,25 @@ inline int grid_for(long long total) {
     if (b > 4096) b = 4096;
     if (b < 1) b = 1;
     return (int)b;
+}
+// the candidates' sort keys into their segments: cursors zeroed, then the LDS-tiled fill, or the row-per-thread one for wide rows
+static int post_fill_keys(const float* prediction, int B, long long N, int n_classes, float conf_thre, bool agn,
+                          const int* seg_offsets, int nseg, int* cursor, unsigned long long* keys, hipStream_t st) {
+    if (hipMemsetAsync(cursor, 0, (size_t)nseg * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
+    const int pitch = (5 + n_classes) | 1;
+    const size_t smem = (size_t)POST_ROWS * pitch * 4;
+    if (5 + n_classes <= POST_MAX_NCH && smem <= 65536) {
+        const long long ntiles = ((long long)B * N + POST_ROWS - 1) / POST_ROWS;
+        auto kern = agn ? post_fill_tiled_kernel<true> : post_fill_tiled_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), smem, st,
+                           prediction, B, N, n_classes, conf_thre, seg_offsets, cursor, keys);
+    } else {
+        auto kern = agn ? post_fill_kernel<true> : post_fill_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3(grid_for((long long)B * N)), dim3(256), 0, st, prediction, B, N,
+                           n_classes, conf_thre, seg_offsets, cursor, keys);
+    }
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
 }
 static bool fill_anchors(Anchors& a, const float* host_wh, int n) {
     if (!host_wh || n < 1 || n > 16) return false;
@@ -2020,20 +2195,7 @@ int y4_post_nms_ex_f32(const float* prediction, int B, long long N, int n_classe
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + l.keys);
     int* cursor = reinterpret_cast<int*>(base + l.cursor);
     hipStream_t st = y4_stream(stream);
-    if (hipMemsetAsync(cursor, 0, (size_t)nseg * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
-    const int pitch = (5 + n_classes) | 1;
-    const size_t smem = (size_t)POST_ROWS * pitch * 4;
-    if (5 + n_classes <= POST_MAX_NCH && smem <= 65536) {
-        const long long ntiles = ((long long)B * N + POST_ROWS - 1) / POST_ROWS;
-        auto kern = agn ? post_fill_tiled_kernel<true> : post_fill_tiled_kernel<false>;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles < 2048 ? ntiles : 2048)), dim3(256), smem, st,
-                           prediction, B, N, n_classes, conf_thre, seg_offsets, cursor, keys);
-    } else {
-        auto kern = agn ? post_fill_kernel<true> : post_fill_kernel<false>;
-        hipLaunchKernelGGL(kern, dim3(grid_for((long long)B * N)), dim3(256), 0, st, prediction, B, N,
-                           n_classes, conf_thre, seg_offsets, cursor, keys);
-    }
-    Y4_CHECK_LAUNCH();
+    if (const int rc = post_fill_keys(prediction, B, N, n_classes, conf_thre, agn, seg_offsets, nseg, cursor, keys, st)) return rc;
     float4* kbox = reinterpret_cast<float4*>(base + l.kbox);
     float* karea = reinterpret_cast<float*>(base + l.karea);
     int* kpos = reinterpret_cast<int*>(base + l.kpos);
@@ -2061,6 +2223,37 @@ int y4_post_nms_f32(const float* prediction, int B, long long N, int n_classes, 
     opts.metric = Y4_NMS_IOU; opts.soft = Y4_SOFT_NONE; opts.sigma = 0.5f;
     return y4_post_nms_ex_f32(prediction, B, N, n_classes, conf_thre, nms_thre, &opts, seg_offsets, total_candidates,
                               det_rows, kept, workspace, workspace_bytes, stream);
+}
+
+size_t y4_post_wbf_workspace(long long total_candidates, int n_segments) {
+    return wbf_ws(total_candidates, n_segments).total;
+}
+
+int y4_post_wbf_f32(const float* prediction, int B, long long N, int n_classes, float conf_thre, float iou_thre, int agnostic,
+                    int n_views, const int* seg_offsets, long long total_candidates, float* det_rows, int* kept,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (!prediction || !seg_offsets || !det_rows || !kept || !workspace) return Y4_ERR_NULL;
+    if (B <= 0 || N <= 0 || N >= (1ll << 31) || n_classes <= 0 || total_candidates < 0 || total_candidates >= (1ll << 31) ||
+        n_views < 1 || (agnostic != 0 && agnostic != 1) || !(iou_thre >= 0.f)) return Y4_ERR_SHAPE;
+    const bool agn = agnostic != 0;
+    if (agn && N * n_classes >= (1ll << 31)) return Y4_ERR_SHAPE;
+    if (!agn && (long long)B * n_classes >= (1ll << 31)) return Y4_ERR_SHAPE;
+    const int nseg = agn ? B : B * n_classes;
+    const WbfWs l = wbf_ws(total_candidates, nseg);
+    if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
+    char* base = static_cast<char*>(workspace);
+    unsigned long long* keys = reinterpret_cast<unsigned long long*>(base + l.keys);
+    int* cursor = reinterpret_cast<int*>(base + l.cursor);
+    hipStream_t st = y4_stream(stream);
+    if (const int rc = post_fill_keys(prediction, B, N, n_classes, conf_thre, agn, seg_offsets, nseg, cursor, keys, st)) return rc;
+    auto kern = agn ? post_wbf_kernel<true> : post_wbf_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3(nseg), dim3(256), 0, st, prediction, N, n_classes, iou_thre, n_views, seg_offsets, keys,
+                       reinterpret_cast<float4*>(base + l.cbox), reinterpret_cast<float*>(base + l.cs),
+                       reinterpret_cast<int*>(base + l.ccls), reinterpret_cast<float4*>(base + l.F),
+                       reinterpret_cast<float4*>(base + l.sum), reinterpret_cast<float*>(base + l.S),
+                       reinterpret_cast<int*>(base + l.cnt), reinterpret_cast<int*>(base + l.cls), det_rows, kept);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
 }
 
 size_t y4_post_topk_workspace(long long total_candidates, int n_segments) {

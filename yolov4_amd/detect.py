@@ -26,6 +26,7 @@ from .yolo.data.jpeg import decode_jpeg_batch
 from .yolo.data.jpeg_enc import encode_jpeg_batch
 from .yolo.data.transform import letterbox_batch, letterbox_mode, val_batch
 from .yolo.model.yololayer import layer_strides
+from .yolo.util.tta import TTAOptions, tta_postprocess, tta_predict, wbf_kwargs
 from .yolo.util.utils import NMSOptions, letterbox2yxyx, postprocess, postprocess_nms, yolobox2yxyx
 from .yolo.util.vis import class_colors, draw_detections
 
@@ -49,7 +50,7 @@ def _read(source):
 
 @torch.no_grad()
 def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None, draw=True, encode=True, batch=8,
-                  nms_options=None, letterbox=None):
+                  nms_options=None, letterbox=None, tta=None):
     """sources: JPEG bytes, paths, or [h, w, 3] uint8 BGR device tensors, in any mix -> one dict per source:
       detections  float64 ndarray [n, 7]: (y1, x1, y2, x2, obj, cls_conf, cls) in SOURCE pixels, postprocess's order
       image       [h, w, 3] uint8 BGR device tensor of the source's size, the detections drawn on it when `draw`
@@ -60,9 +61,13 @@ def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None
     batches of `batch` images, and left in eval mode.  `nms_options` (an NMSOptions or a dict of postprocess_nms's keywords):
     DIoU- / Soft- / class-agnostic NMS and the per-image cap; None is the reference's postprocess.
     `letterbox`: None stretches every image to S x S (the reference's rule); 'square' | 'rect' keep its aspect on a grey
-    canvas, S x S or -- chosen per chunk of `batch` sources -- only as large as the chunk needs, and clip boxes to the image."""
+    canvas, S x S or -- chosen per chunk of `batch` sources -- only as large as the chunk needs, and clip boxes to the image.
+    `tta` (a TTAOptions): the model runs on rescaled / mirrored views of each batch -- of the padded canvas when letterboxed --
+    and the predictions are merged by NMS or weighted box fusion (yolo/util/tta.py); None: one forward pass, as ever."""
     if nms_options is not None and not isinstance(nms_options, dict):
         nms_options = nms_options.kwargs()
+    if tta is not None and tta.merge == 'wbf':
+        wbf_kwargs(nms_options)                             # a ValueError before any work
     letterbox = letterbox_mode(letterbox)
     max_stride = max(layer_strides(cfg['MODEL'], [8, 16, 32])) if letterbox is not None else None
     conf_thre = cfg['TEST']['CONFTHRE'] if conf_thre is None or conf_thre < 0 else conf_thre
@@ -93,7 +98,9 @@ def detect_images(model, cfg, sources, conf_thre=None, nms_thre=None, names=None
             x, infos = val_batch(images, img_size)
         else:
             x, infos = letterbox_batch(images, img_size, letterbox, max_stride)
-        if nms_options is None:
+        if tta is not None:
+            dets = tta_postprocess(tta_predict(model, x, tta), num_classes, conf_thre, nms_thre, tta, nms_options)
+        elif nms_options is None:
             dets = postprocess(model(x), num_classes, conf_thre=conf_thre, nms_thre=nms_thre)
         else:
             dets = postprocess_nms(model(x), num_classes, conf_thre=conf_thre, nms_thre=nms_thre, **nms_options)
@@ -167,6 +174,11 @@ def build_parser():
     ap.add_argument('--max-det', type=int, default=None)
     # a flag that is given overrides the cfg's TEST.LETTERBOX (off | square | rect; absent: off, the reference's stretch)
     ap.add_argument('--letterbox', choices=['off', 'square', 'rect'], default=None)
+    # test-time augmentation: --tta turns it on (the cfg's TEST.TTA, else the defaults); the other flags override its fields
+    ap.add_argument('--tta', action='store_true', default=None)
+    ap.add_argument('--tta-scales', default=None, help='comma-separated, e.g. 1,0.83,0.67')
+    ap.add_argument('--tta-flips', default=None, help='comma-separated 0/1, one per scale, e.g. 0,1,0')
+    ap.add_argument('--tta-merge', choices=['nms', 'wbf'], default=None)
     return ap
 
 
@@ -174,6 +186,24 @@ def letterbox_from_args(args, cfg):
     """--letterbox when given, else the cfg's optional TEST.LETTERBOX; None for 'off' / absent."""
     v = args.letterbox if args.letterbox is not None else (cfg.get('TEST') or {}).get('LETTERBOX')
     return letterbox_mode(v)
+
+
+def tta_from_args(args, cfg):
+    """The cfg's optional TEST.TTA with the command line's on top; None when neither asks for it.  Any --tta* flag turns it on."""
+    o = TTAOptions.from_cfg(cfg)
+    if o is None and not args.tta and args.tta_scales is None and args.tta_flips is None and args.tta_merge is None:
+        return None
+    o = o or TTAOptions()
+    over = {}
+    if args.tta_scales is not None:
+        over['scales'] = tuple(float(v) for v in args.tta_scales.split(','))
+        if args.tta_flips is None and len(over['scales']) != len(o.flips):
+            over['flips'] = (False,) * len(over['scales'])
+    if args.tta_flips is not None:
+        over['flips'] = tuple(v.strip().lower() in ('1', 'true', 'yes') for v in args.tta_flips.split(','))
+    if args.tta_merge is not None:
+        over['merge'] = args.tta_merge
+    return dataclasses.replace(o, **over)
 
 
 def nms_options_from_args(args, cfg):
@@ -213,7 +243,8 @@ def main(argv=None):
     save_dir = increment_path(os.path.join(args.dest, 'exp'))
     os.makedirs(save_dir)
     out = detect_images(model, cfg, paths, args.conf_thre, args.nms_thre, names=args.names, batch=args.batch,
-                        nms_options=nms_options_from_args(args, cfg), letterbox=letterbox_from_args(args, cfg))
+                        nms_options=nms_options_from_args(args, cfg), letterbox=letterbox_from_args(args, cfg),
+                        tta=tta_from_args(args, cfg))
     for path, r in zip(paths, out):
         target = os.path.join(save_dir, os.path.splitext(os.path.basename(path))[0] + '.jpg')
         with open(target, 'wb') as f:

@@ -17,6 +17,7 @@ import torch.distributed as dist
 
 from ..optim.lr_schedulers.build import adjust_learning_rate
 from ... import trace
+from ..util.tta import tta_postprocess, tta_predict, wbf_kwargs
 from ..util.utils import detections_to_coco, postprocess, postprocess_nms
 
 
@@ -118,7 +119,7 @@ def _img_infos(info, batch):
 
 @torch.no_grad()
 def validate(val_loader, model, conf_threshold, nms_threshold, device=None, evaluator=None, num_classes=80,
-             nms_options=None):
+             nms_options=None, tta=None):
     """build.py:111-190.  Returns (AP50_95, AP50) from `evaluator(records, image_ids)` when one is given (the
     reference calls pycocotools' COCOeval there); without one returns (0, 0) like the reference's empty branch and
     leaves the COCO-format records on `validate.records`.  `yolo/util/cocoeval.py::COCOEvaluator(annotations)` is such an
@@ -127,9 +128,13 @@ def validate(val_loader, model, conf_threshold, nms_threshold, device=None, eval
     dict of postprocess_nms's keywords) selects DIoU- / Soft- / class-agnostic NMS and the per-image cap; None is the
     reference's postprocess.  A loader that letterboxes its input (COCOBatchLoader(letterbox=...)) adds target['pad'], B rows
     of (top, left), and img_info rows [h, w, nh, nw, id, ...]: boxes then go back through letterbox2xywh, clipped to the
-    image; without the key nothing changes."""
+    image; without the key nothing changes.  `tta` (a TTAOptions, yolo/util/tta.py): every batch is run as rescaled /
+    mirrored views (of the padded canvas when letterboxed) and the predictions merged by NMS or weighted box fusion; None:
+    one forward pass, the calls above."""
     if nms_options is not None and not isinstance(nms_options, dict):
         nms_options = nms_options.kwargs()
+    if tta is not None and tta.merge == 'wbf':
+        wbf_kwargs(nms_options)                             # a ValueError before any work
     model.eval()
     ids, data_list = [], []
     class_ids = getattr(getattr(val_loader, 'dataset', None), 'class_ids', None)
@@ -140,9 +145,14 @@ def validate(val_loader, model, conf_threshold, nms_threshold, device=None, eval
         if pads is not None:
             pads = [[float(v) for v in (p.tolist() if hasattr(p, 'tolist') else p)] for p in pads]
         with trace.range('y4.eval_forward'):
-            outputs = model(img.to(device) if device is not None else img)                        # :133
+            if tta is not None:
+                outputs = tta_predict(model, img.to(device) if device is not None else img, tta)
+            else:
+                outputs = model(img.to(device) if device is not None else img)                    # :133
         with trace.range('y4.postprocess'):
-            if nms_options is None:
+            if tta is not None:
+                outputs = tta_postprocess(outputs, num_classes, conf_threshold, nms_threshold, tta, nms_options)
+            elif nms_options is None:
                 outputs = postprocess(outputs, num_classes, conf_threshold, nms_threshold)        # :137
             else:
                 outputs = postprocess_nms(outputs, num_classes, conf_threshold, nms_threshold, **nms_options)

@@ -10,6 +10,7 @@ unstable numpy argsort and is platform dependent.
 
 postprocess_nms() is the same pipeline with a DIoU measure, Soft-NMS, class-agnostic
 segments and a per-image cap; postprocess() stays the reference's rule.
+postprocess_wbf() runs weighted box fusion on those stages instead of suppression.
 """
 import ctypes
 import dataclasses
@@ -142,34 +143,30 @@ class NMSOptions:
         return dataclasses.asdict(self)
 
 
-def postprocess_nms(prediction, num_classes, conf_thre=0.7, nms_thre=0.45, *, metric='iou', soft=None, sigma=0.5,
-                    agnostic=False, max_det=0):
-    """postprocess() with options (DESIGN.md section 15): metric 'iou' | 'diou', soft None | 'linear' | 'gaussian' (Soft-NMS,
-    `sigma` for the Gaussian decay), agnostic (all classes of an image compete), max_det (rows kept per image, 0: all).
-    Same return contract and in-place xyxy side effect; with the defaults the same kernels run and the result is
-    bit-identical.  Soft-NMS rows carry cls_conf * W, so row[4] * row[5] is the decayed score."""
-    o = NMSOptions(metric, soft, sigma, agnostic, max_det)
+def _postprocess_segments(what, prediction, num_classes, conf_thre, agnostic, max_det, stage):
+    """The stages postprocess_nms() and postprocess_wbf() share: candidate count, then -- with the capacity retry and the one
+    host read -- scan, `stage(L, prediction, B, N, seg_off, cap, rows, kept, nseg, stream)` (key fill, sort and suppression or
+    fusion into rows / kept) and compaction or the per-image top-k.  Return contract and in-place xyxy side effect of postprocess()."""
     L = lib()
     src = prediction
     on_host = not prediction.is_cuda
     if on_host:
         prediction = prediction.to(_dev())
     if prediction.dtype != torch.float32 or not prediction.is_contiguous():
-        raise ops.Y4Error('postprocess_nms expects a contiguous float32 [B,N,5+C] tensor')
+        raise ops.Y4Error(what + ' expects a contiguous float32 [B,N,5+C] tensor')
     B, N, n_ch = prediction.shape
     if n_ch != 5 + num_classes:
-        raise ops.Y4Error('postprocess_nms: last dim must be 5 + num_classes')
+        raise ops.Y4Error(what + ': last dim must be 5 + num_classes')
     dev = prediction.device
     out = [None for _ in range(B)]
     if N == 0 or B == 0:
         return out
-    opts = NmsOpts(NMS_METRICS[o.metric], NMS_SOFT[o.soft], float(o.sigma), int(bool(o.agnostic)), int(o.max_det))
-    popts = ctypes.addressof(opts)
-    per_img = 1 if o.agnostic else num_classes
+    agnostic = int(bool(agnostic))
+    per_img = 1 if agnostic else num_classes
     nseg = B * per_img
     counts = torch.empty(nseg, dtype=torch.int32, device=dev)
     st = ops._stream()
-    check(L.y4_post_count_ex_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), 1, opts.agnostic,
+    check(L.y4_post_count_ex_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), 1, agnostic,
                                  ops._ptr(counts), st), 'post_count_ex')
     if on_host:
         src[:, :, :4] = prediction[:, :, :4].cpu()
@@ -183,15 +180,11 @@ def postprocess_nms(prediction, num_classes, conf_thre=0.7, nms_thre=0.45, *, me
         check(L.y4_post_scan_i32(ops._ptr(counts), nseg, cap, ops._ptr(seg_off), ops._ptr(meta), st), 'post_scan')
         rows = torch.empty((cap, 7), dtype=torch.float32, device=dev)
         final = torch.empty((cap, 7), dtype=torch.float32, device=dev)
-        nbytes = L.y4_post_nms_ex_workspace(cap, nseg, popts)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(L.y4_post_nms_ex_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), float(nms_thre), popts,
-                                   ops._ptr(seg_off), cap, ops._ptr(rows), ops._ptr(kept), ops._ptr(ws), nbytes, st),
-              'post_nms_ex')
-        if o.max_det > 0:
+        stage(L, prediction, B, N, seg_off, cap, rows, kept, nseg, st)
+        if max_det > 0:
             tbytes = L.y4_post_topk_workspace(cap, nseg)
             tws = torch.empty(tbytes, dtype=torch.uint8, device=dev)
-            check(L.y4_post_topk_compact_f32(ops._ptr(rows), ops._ptr(seg_off), ops._ptr(kept), B, per_img, int(o.max_det),
+            check(L.y4_post_topk_compact_f32(ops._ptr(rows), ops._ptr(seg_off), ops._ptr(kept), B, per_img, int(max_det),
                                              cap, ops._ptr(final), ops._ptr(out_off), ops._ptr(meta[2:]), ops._ptr(tws),
                                              tbytes, st), 'post_topk_compact')
         else:
@@ -212,6 +205,47 @@ def postprocess_nms(prediction, num_classes, conf_thre=0.7, nms_thre=0.45, *, me
         if img_off[b + 1] > img_off[b]:
             out[b] = dets[img_off[b]:img_off[b + 1]]
     return out
+
+
+def postprocess_nms(prediction, num_classes, conf_thre=0.7, nms_thre=0.45, *, metric='iou', soft=None, sigma=0.5,
+                    agnostic=False, max_det=0):
+    """postprocess() with options (DESIGN.md section 15): metric 'iou' | 'diou', soft None | 'linear' | 'gaussian' (Soft-NMS,
+    `sigma` for the Gaussian decay), agnostic (all classes of an image compete), max_det (rows kept per image, 0: all).
+    Same return contract and in-place xyxy side effect; with the defaults the same kernels run and the result is
+    bit-identical.  Soft-NMS rows carry cls_conf * W, so row[4] * row[5] is the decayed score."""
+    o = NMSOptions(metric, soft, sigma, agnostic, max_det)
+    opts = NmsOpts(NMS_METRICS[o.metric], NMS_SOFT[o.soft], float(o.sigma), int(bool(o.agnostic)), int(o.max_det))
+    popts = ctypes.addressof(opts)
+
+    def stage(L, pred, B, N, seg_off, cap, rows, kept, nseg, st):
+        nbytes = L.y4_post_nms_ex_workspace(cap, nseg, popts)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+        check(L.y4_post_nms_ex_f32(ops._ptr(pred), B, N, num_classes, float(conf_thre), float(nms_thre), popts,
+                                   ops._ptr(seg_off), cap, ops._ptr(rows), ops._ptr(kept), ops._ptr(ws), nbytes, st),
+              'post_nms_ex')
+    return _postprocess_segments('postprocess_nms', prediction, num_classes, conf_thre, o.agnostic, int(o.max_det), stage)
+
+
+def postprocess_wbf(prediction, num_classes, conf_thre, iou_thre=0.55, *, views=1, agnostic=False, max_det=0):
+    """Weighted box fusion on postprocess_nms()'s stages: overlapping candidates of a segment are
+    averaged (score-weighted) instead of suppressed.  `views`: how many predictions per object the input holds (the number of
+    TTA views); a cluster with fewer members has its score scaled by members / views.  Rows are
+    (x1, y1, x2, y2, 1.0, fused score, cls), so row[4] * row[5] is the score; the return contract, the in-place xyxy side
+    effect, the capacity retry and the one host read are postprocess_nms()'s.  No CPU path."""
+    if int(views) < 1:
+        raise ValueError('views must be >= 1')
+    if int(max_det) < 0:
+        raise ValueError('max_det must be >= 0 (0: no cap)')
+    if not float(iou_thre) >= 0:
+        raise ValueError('iou_thre must be >= 0')
+    agn = int(bool(agnostic))
+
+    def stage(L, pred, B, N, seg_off, cap, rows, kept, nseg, st):
+        nbytes = L.y4_post_wbf_workspace(cap, nseg)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+        check(L.y4_post_wbf_f32(ops._ptr(pred), B, N, num_classes, float(conf_thre), float(iou_thre), agn, int(views),
+                                ops._ptr(seg_off), cap, ops._ptr(rows), ops._ptr(kept), ops._ptr(ws), nbytes, st), 'post_wbf')
+    return _postprocess_segments('postprocess_wbf', prediction, num_classes, conf_thre, agn, int(max_det), stage)
 
 
 # ------------------------------------------------------------------ detections -> COCO records (SURVEY 8f row 4)
