@@ -556,6 +556,55 @@ int y4_yolo_box_loss_bwd_ex_f32(const float* pred, int box_kind, float gain, con
                                 int B, int F, int A, int K, int n_classes, float iou_thresh, float scale_xy,
                                 const void* workspace, size_t workspace_bytes, void* stream);
 
+/* Focal loss, IoU-aware objectness and objectness / class gains of the loss.  The four entries below are the _ex entries
+ * with every option of the dense loss in one plain struct; the entries above forward to them with the defaults
+ *   iou_thresh 1, label_smooth 0, focal_gamma 0, focal_alpha 0.25, focal_terms 3, obj_iou_ratio 0,
+ *   obj_iou_kind Y4_BOX_CIOU, obj_gain 1, cls_gain 1
+ * and give the bits they always gave: with focal_gamma = 0, obj_iou_ratio = 0 and both gains 1 the kernels that run
+ * are the ones in which the options do not exist.  Nothing is stored in the workspace about the options: pass every
+ * later call the same opts the forward got.  y4_yolo_loss_mask_output*_f32 and y4_yolo_box_loss_*_f32 do not depend
+ * on them; they accept the larger workspace.
+ *
+ * With o the value in `output` (the decode's fp32 sigmoid), t the element's target, bce / bce_grad the terms of the
+ * entries above (logs clamped at -100, denominator guarded by 1e-12), all in fp32:
+ * focal_gamma 0 (off) or in [0.5, 5]; focal_alpha 0 (no class balance) or in (0, 1); focal_terms bit 0: objectness,
+ *   bit 1: classes (alpha and terms are not looked at with gamma = 0).  The soft-target focal term of YOLOv5:
+ *     p_t = t o + (1 - t)(1 - o), q = 1 - p_t, a = alpha > 0 ? t alpha + (1 - t)(1 - alpha) : 1,
+ *     FL = (bce a) q^gamma,   dFL/do = a (bce_grad q^gamma - ((bce gamma) q^(gamma - 1)) (2 t - 1)),
+ *   the exact derivative; both are 0 at q = 0.  Objectness: every cell with obj_mask != 0; classes: every class element
+ *   of a positive record, against the smoothed targets.
+ * obj_iou_ratio r in [0, 1]; above 0, the objectness target of a cell with a record is (1 - r) + r max(X, 0), X =
+ *   1 - (the box loss of kind obj_iou_kind on that record), on the operands and with the bits of y4_yolo_box_loss_fwd.
+ *   A NaN X (a NaN in the cell's pred) makes the target, the cell's objectness loss and gradient and loss_parts[2] NaN.
+ *   X is a constant in the backward.  The targets are kept in pos_obj [B, R] floats, appended to the workspace after
+ *   pos_box (y4_yolo_loss_workspace_opts; with r = 0 the size is y4_yolo_loss_workspace_ex's and nothing touches the
+ *   array); target[..., 4] of the dense targets holds them.
+ * obj_gain, cls_gain finite and > 0: loss_parts[2] and [3] are multiplied once, in fp64, after the reduction; the
+ *   gradient is ((g gain) *gscale) on channel 4 / the class channels.
+ * Errors before any launch: NULL pointer (opts included) Y4_ERR_NULL; an option out of range (NaN included)
+ * Y4_ERR_SHAPE, 0 from the size query. */
+typedef struct y4_loss_opts {
+    float iou_thresh, label_smooth;
+    float focal_gamma, focal_alpha;
+    int   focal_terms;       /* bit 0: obj, bit 1: cls */
+    float obj_iou_ratio;
+    int   obj_iou_kind;      /* Y4_BOX_IOU .. Y4_BOX_CIOU */
+    float obj_gain, cls_gain;
+} y4_loss_opts;      /* 36 bytes */
+size_t y4_yolo_loss_workspace_opts(int B, int F, int A, int K, int n_classes, const y4_loss_opts* opts /* host */);
+int y4_yolo_loss_fwd_opts_f32(const float* output, const float* pred, const float* labels, int K,
+                              int B, int F, int A, int n_classes, float stride, float ignore_thresh,
+                              const float* all_anchors_host, int n_all_anchors, const int* anch_mask_host,
+                              const y4_loss_opts* opts, float* obj_mask, double* loss_parts,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int y4_yolo_loss_bwd_opts_f32(const float* output, int output_is_masked, const float* obj_mask,
+                              const float* gscale, float* g_output,
+                              int B, int F, int A, int K, int n_classes, const y4_loss_opts* opts,
+                              const void* workspace, size_t workspace_bytes, void* stream);
+int y4_yolo_loss_dense_targets_opts_f32(float* target, float* tgt_mask, float* tgt_scale,
+                                        int B, int F, int A, int K, int n_classes, const y4_loss_opts* opts,
+                                        const void* workspace, size_t workspace_bytes, void* stream);
+
 /* Device-side prefix sums of postprocess (no host round trip between its stages):
  * y4_post_scan_i32: seg_offsets[0..n_segments] = exclusive scan of the candidate counts, clamped to `cap` (the capacity, in
  *   candidates, of the buffers the caller allocated: a too-small capacity truncates segments, it never overflows);

@@ -109,6 +109,10 @@ PROTOTYPES = {
     'y4_yolo_loss_dense_targets_ex_f32': (I, [P, P, P, I, I, I, I, I, F, F, P, Z, P]),
     'y4_yolo_box_loss_fwd_ex_f32': (I, [P, I, F, I, I, I, I, I, F, P, P, Z, P]),
     'y4_yolo_box_loss_bwd_ex_f32': (I, [P, I, F, P, P, I, I, I, I, I, F, F, P, Z, P]),
+    'y4_yolo_loss_workspace_opts': (Z, [I, I, I, I, I, P]),
+    'y4_yolo_loss_fwd_opts_f32': (I, [P, P, P, I, I, I, I, I, F, F, P, I, P, P, P, P, P, Z, P]),
+    'y4_yolo_loss_bwd_opts_f32': (I, [P, I, P, P, P, I, I, I, I, I, P, P, Z, P]),
+    'y4_yolo_loss_dense_targets_opts_f32': (I, [P, P, P, I, I, I, I, I, P, P, Z, P]),
     'y4_post_count_f32': (I, [P, I, L, I, F, I, P, P]),
     'y4_post_scan_i32': (I, [P, I, L, P, P, P]),
     'y4_post_compact_f32': (I, [P, P, P, I, I, P, P, P, P]),
@@ -182,6 +186,16 @@ class NmsOpts(ctypes.Structure):
     """y4_nms_opts (32 bytes)"""
     _fields_ = [('metric', c_int), ('soft', c_int), ('sigma', c_float), ('agnostic', c_int), ('max_det', c_int),
                 ('reserved', c_int * 3)]
+
+
+FOCAL_TERMS = {'obj': 1, 'cls': 2, 'obj+cls': 3}
+
+
+class LossOpts(ctypes.Structure):
+    """y4_loss_opts (36 bytes)"""
+    _fields_ = [('iou_thresh', c_float), ('label_smooth', c_float), ('focal_gamma', c_float), ('focal_alpha', c_float),
+                ('focal_terms', c_int), ('obj_iou_ratio', c_float), ('obj_iou_kind', c_int), ('obj_gain', c_float),
+                ('cls_gain', c_float)]
 
 
 class AugSrc(ctypes.Structure):

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(256) void bboxes_iou_kernel(const float* __restrict
 
 // ------------------------------------------------------------------------------------ loss
 struct LossWs {
-    size_t nlabel, npos, truth, pos_cell, pos_val, pos_cls, pos_index, partials, pos_box, total;
+    size_t nlabel, npos, truth, pos_cell, pos_val, pos_cls, pos_index, partials, pos_box, pos_obj, total;
     int cw, nblocks;
 };
 static inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
@@ -293,7 +293,8 @@ static inline bool loss_opts_ok(float iou_thresh, float label_smooth) {         
     return iou_thresh > 0.f && iou_thresh <= 1.f && label_smooth >= 0.f && label_smooth < 1.f;
 }
 static inline bool scale_xy_ok(float s) { return s >= 1.f && s <= 2.f; }
-static LossWs loss_ws(int B, int F, int A, int K, int C, int R) {
+// iou_obj (obj_iou_ratio > 0): pos_obj [B, R] is appended; without it offsets and total are what they were.
+static LossWs loss_ws(int B, int F, int A, int K, int C, int R, bool iou_obj = false) {
     LossWs w;
     w.cw = (C + 31) / 32;
     const long long cells = (long long)B * A * F * F;
@@ -308,6 +309,8 @@ static LossWs loss_ws(int B, int F, int A, int K, int C, int R) {
     w.pos_index = o; o = al16(o + (size_t)cells * 4);
     w.partials = o; o = al16(o + (size_t)w.nblocks * 4 * 8);
     w.pos_box = o; o = al16(o + (size_t)B * R * 4 * 4);       // appended: every offset above is what it was without it
+    w.pos_obj = o;
+    if (iou_obj) o = al16(o + (size_t)B * R * 4);
     w.total = o;
     return w;
 }
@@ -330,6 +333,52 @@ static LossPtrs loss_ptrs(const void* ws, const LossWs& l) {
     p.partials = reinterpret_cast<double*>(b + l.partials);
     p.pos_box = reinterpret_cast<float*>(b + l.pos_box);
     return p;
+}
+
+// What the kernels need of the options.  fobj / fcls: the objectness / class BCE terms are focal (gamma > 0 and the bit
+// of focal_terms).  r > 0: the objectness target of a record is (1 - r) + r * max(X, 0), kept per record in pos_obj.
+struct LossOptK {
+    float gamma, alpha;
+    int fobj, fcls;
+    float r;
+    int kind;
+    float obj_gain, cls_gain;
+    float* pos_obj;                                            // [B, R]; NULL with r = 0
+};
+
+// y4_loss_opts: the defaults with the two options of the _ex entries; the range check (false for NaN too; alpha, the
+// term bits and the kind count only where gamma / the ratio switch them on); whether anything beyond the _ex options is
+// on, i.e. whether the option kernels have to run at all.
+static inline y4_loss_opts loss_opts_default(float iou_thresh, float label_smooth) {
+    y4_loss_opts o;
+    o.iou_thresh = iou_thresh; o.label_smooth = label_smooth;
+    o.focal_gamma = 0.f; o.focal_alpha = 0.25f; o.focal_terms = 3;
+    o.obj_iou_ratio = 0.f; o.obj_iou_kind = Y4_BOX_CIOU;
+    o.obj_gain = 1.f; o.cls_gain = 1.f;
+    return o;
+}
+static inline bool gain_ok(float g) { return g > 0.f && g <= 3.402823466e38f; }
+static bool loss_opts_all_ok(const y4_loss_opts* o) {
+    if (!loss_opts_ok(o->iou_thresh, o->label_smooth)) return false;
+    const float g = o->focal_gamma, a = o->focal_alpha, r = o->obj_iou_ratio;
+    if (!(g == 0.f || (g >= 0.5f && g <= 5.f))) return false;
+    if (g > 0.f && (!(a >= 0.f && a < 1.f) || o->focal_terms < 1 || o->focal_terms > 3)) return false;
+    if (!(r >= 0.f && r <= 1.f)) return false;
+    if (r > 0.f && (o->obj_iou_kind < Y4_BOX_IOU || o->obj_iou_kind > Y4_BOX_CIOU)) return false;
+    return gain_ok(o->obj_gain) && gain_ok(o->cls_gain);
+}
+static inline bool loss_opts_any(const y4_loss_opts* o) {
+    return o->focal_gamma > 0.f || o->obj_iou_ratio > 0.f || o->obj_gain != 1.f || o->cls_gain != 1.f;
+}
+static LossOptK loss_opt_k(const y4_loss_opts* o, const void* ws, const LossWs& l) {
+    LossOptK k;
+    k.gamma = o->focal_gamma; k.alpha = o->focal_alpha;
+    k.fobj = (o->focal_gamma > 0.f && (o->focal_terms & 1)) ? 1 : 0;
+    k.fcls = (o->focal_gamma > 0.f && (o->focal_terms & 2)) ? 1 : 0;
+    k.r = o->obj_iou_ratio; k.kind = o->obj_iou_kind;
+    k.obj_gain = o->obj_gain; k.cls_gain = o->cls_gain;
+    k.pos_obj = o->obj_iou_ratio > 0.f ? reinterpret_cast<float*>(static_cast<char*>(const_cast<void*>(ws)) + l.pos_obj) : nullptr;
+    return k;
 }
 
 // yololoss.py:196-265,304-369: one thread per image walks its <= K labels in order (the
@@ -615,10 +664,47 @@ __device__ __forceinline__ float bce_term(float o, float t) {
 }
 __device__ __forceinline__ float bce_grad(float o, float t) { return (o - t) / fmaxf((1.0f - o) * o, 1e-12f); }
 
+// ---- focal loss, IoU-aware objectness, obj / cls gains (y4_loss_opts)
+// The soft-target focal term of YOLOv5 on one element: with p_t = t o + (1 - t)(1 - o), q = 1 - p_t and
+// a = alpha > 0 ? t alpha + (1 - t)(1 - alpha) : 1 the loss is (bce a) q^gamma and its exact derivative
+// a (bce_grad q^gamma - ((bce gamma) q^(gamma - 1)) (2 t - 1)); both are 0 at q = 0.  q^(gamma - 1) is
+// exp2(e log2 q), relative error about |e log2 q| 2^-24 (at most 6e-6 at q = 2^-24, gamma = 5), and q^gamma is that
+// times q: one transcendental pair per element for both powers.
+struct FocalW { float a, m, m1; };
+__device__ __forceinline__ FocalW focal_weights(float o, float t, float gamma, float alpha) {
+    const float pt = t * o + (1.0f - t) * (1.0f - o);
+    const float q = 1.0f - pt;
+    FocalW f;
+    f.a = alpha > 0.f ? t * alpha + (1.0f - t) * (1.0f - alpha) : 1.0f;
+    f.m1 = q > 0.f ? exp2f((gamma - 1.0f) * log2f(q)) : 0.f;
+    f.m = q > 0.f ? f.m1 * q : 0.f;
+    return f;
+}
+__device__ __forceinline__ float focal_term(float o, float t, float gamma, float alpha) {
+    const FocalW f = focal_weights(o, t, gamma, alpha);
+    return (bce_term(o, t) * f.a) * f.m;
+}
+__device__ __forceinline__ float focal_grad(float o, float t, float gamma, float alpha) {
+    const FocalW f = focal_weights(o, t, gamma, alpha);
+    return f.a * (bce_grad(o, t) * f.m - ((bce_term(o, t) * gamma) * f.m1) * (2.0f * t - 1.0f));
+}
+
+struct BoxTerm { float loss, g0, g1, g2, g3; };                // g: d loss / d(px, py, log pw, log ph)
+template <bool GRAD>
+__device__ __forceinline__ BoxTerm box_term(int kind, float px, float py, float pw, float ph, float tx, float ty,
+                                            float tw, float th);
+
+// The option kernels take a LossOptK as their last argument, the default instances (OPT = false) nothing: those keep the
+// arguments and the code they had before the options existed.
+__device__ __forceinline__ LossOptK loss_opt_of() { return LossOptK{}; }
+__device__ __forceinline__ LossOptK loss_opt_of(const LossOptK& op) { return op; }
+
 // yololoss.py:276-301 (ignore mask) + :402-427 (loss terms), one thread per cell.
+template <bool OPT, typename... Op>
 __global__ __launch_bounds__(LOSS_BLOCK) void yolo_loss_dense_kernel(
     const float* __restrict__ output, const float* __restrict__ pred, int B, int F, int A, int K, int R, int C, int cw,
-    float thresh, float cls_lo, float cls_hi, float* __restrict__ obj_mask, LossPtrs w) {
+    float thresh, float cls_lo, float cls_hi, float* __restrict__ obj_mask, LossPtrs w, Op... opk) {
+    const LossOptK op = loss_opt_of(opk...);
     __shared__ double red[4][LOSS_BLOCK / 64];
     const long long cells = (long long)B * A * F * F;
     const long long cell = (long long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
@@ -651,7 +737,24 @@ __global__ __launch_bounds__(LOSS_BLOCK) void yolo_loss_dense_kernel(
         const float m = (rec >= 0 || !ignore) ? 1.f : 0.f;
         obj_mask[cell] = m;
         const float* o = output + cell * n_ch;
-        if (m != 0.f) part[2] = (double)bce_term(o[4], rec >= 0 ? 1.f : 0.f);
+        float t_obj = rec >= 0 ? 1.f : 0.f;
+        if (OPT) {
+            if (rec >= 0 && op.r > 0.f) {
+                // X on box_record()'s operands: both boxes relative to the cell origin, so the bits are the box loss's
+                const int c = (int)(cell - (long long)b * per_img);
+                const float fi = (float)(c % F), fj = (float)((c / F) % F);
+                const float* tb = w.pos_box + ((long long)b * R + rec) * 4;
+                const float x = 1.0f - box_term<false>(op.kind, px - fi, py - fj, pw, ph, tb[0] - fi, tb[1] - fj, tb[2],
+                                                       tb[3]).loss;
+                t_obj = (1.0f - op.r) + op.r * fmaxf(x, 0.f);
+                if (x != x) t_obj = NAN;                       // fmaxf drops the NaN of a NaN pred
+                op.pos_obj[(long long)b * R + rec] = t_obj;
+            }
+        }
+        if (m != 0.f) {
+            if (OPT && op.fobj) part[2] = (double)focal_term(o[4], t_obj, op.gamma, op.alpha);
+            else part[2] = (double)bce_term(o[4], t_obj);
+        }
         if (rec >= 0) {
             const float* pv = w.pos_val + ((long long)b * R + rec) * 5;
             const unsigned* pc = w.pos_cls + ((long long)b * R + rec) * cw;
@@ -661,7 +764,12 @@ __global__ __launch_bounds__(LOSS_BLOCK) void yolo_loss_dense_kernel(
             const float d2 = o[2] * s - pv[2] * s, d3 = o[3] * s - pv[3] * s;
             part[1] = ((double)(d2 * d2) + (double)(d3 * d3)) * 0.5;
             double c = 0;
-            for (int k = 0; k < C; ++k) c += (double)bce_term(o[5 + k], ((pc[k >> 5] >> (k & 31)) & 1u) ? cls_hi : cls_lo);
+            if (OPT && op.fcls) {
+                for (int k = 0; k < C; ++k)
+                    c += (double)focal_term(o[5 + k], ((pc[k >> 5] >> (k & 31)) & 1u) ? cls_hi : cls_lo, op.gamma, op.alpha);
+            } else {
+                for (int k = 0; k < C; ++k) c += (double)bce_term(o[5 + k], ((pc[k >> 5] >> (k & 31)) & 1u) ? cls_hi : cls_lo);
+            }
             part[3] = c;
         }
     }
@@ -680,8 +788,11 @@ __global__ __launch_bounds__(LOSS_BLOCK) void yolo_loss_dense_kernel(
     }
 }
 
+// GAIN: parts[2] *= obj_gain, parts[3] *= cls_gain, once, in fp64, on the reduced sums
+template <bool GAIN, typename... Op>
 __global__ __launch_bounds__(256) void yolo_loss_final_kernel(const double* __restrict__ partials, int nblocks,
-                                                              double* __restrict__ out) {
+                                                              double* __restrict__ out, Op... opk) {
+    const LossOptK op = loss_opt_of(opk...);
     __shared__ double red[4][256];
     double v[4] = {0, 0, 0, 0};
     for (int i = threadIdx.x; i < nblocks; i += 256)
@@ -696,15 +807,25 @@ __global__ __launch_bounds__(256) void yolo_loss_final_kernel(const double* __re
             for (int q = 0; q < 4; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x < 4) out[threadIdx.x] = red[threadIdx.x][0];
+    if (threadIdx.x < 4) {
+        double v = red[threadIdx.x][0];
+        if (GAIN) {
+            if (threadIdx.x == 2) v = v * (double)op.obj_gain;
+            if (threadIdx.x == 3) v = v * (double)op.cls_gain;
+        }
+        out[threadIdx.x] = v;
+    }
 }
 
-// grad wrt `output`, dense: thread per element
+// grad wrt `output`, dense: thread per element.  OPT as in yolo_loss_dense_kernel.
+template <bool OPT, typename... Op>
 __global__ __launch_bounds__(256) void yolo_loss_bwd_kernel(const float* __restrict__ output, int masked,
                                                             const float* __restrict__ obj_mask,
                                                             const float* __restrict__ gscale_p,
                                                             float* __restrict__ g_out, int B, int F, int A, int R,
-                                                            int C, int cw, float cls_lo, float cls_hi, LossPtrs w) {
+                                                            int C, int cw, float cls_lo, float cls_hi, LossPtrs w,
+                                                            Op... opk) {
+    const LossOptK op = loss_opt_of(opk...);
     const int n_ch = 5 + C;
     const long long total = (long long)B * A * F * F * n_ch;
     const int per_img = A * F * F;
@@ -716,7 +837,16 @@ __global__ __launch_bounds__(256) void yolo_loss_bwd_kernel(const float* __restr
         const int rec = w.pos_index[cell];
         float g = 0.f;
         if (ch == 4) {
-            if (obj_mask[cell] != 0.f) g = bce_grad(output[e], rec >= 0 ? 1.f : 0.f);
+            if (obj_mask[cell] != 0.f) {
+                float t = rec >= 0 ? 1.f : 0.f;
+                if (OPT) {
+                    if (rec >= 0 && op.r > 0.f) t = op.pos_obj[(long long)(cell / per_img) * R + rec];
+                    g = op.fobj ? focal_grad(output[e], t, op.gamma, op.alpha) : bce_grad(output[e], t);
+                    g = g * op.obj_gain;
+                } else {
+                    g = bce_grad(output[e], t);
+                }
+            }
         } else if (rec >= 0) {
             const int b = (int)(cell / per_img);
             const float* pv = w.pos_val + ((long long)b * R + rec) * 5;
@@ -727,12 +857,19 @@ __global__ __launch_bounds__(256) void yolo_loss_bwd_kernel(const float* __restr
             else {
                 const int k = ch - 5;
                 const unsigned bit = (w.pos_cls[((long long)b * R + rec) * cw + (k >> 5)] >> (k & 31)) & 1u;
-                g = bce_grad(o, bit ? cls_hi : cls_lo);
+                if (OPT) {
+                    g = op.fcls ? focal_grad(o, bit ? cls_hi : cls_lo, op.gamma, op.alpha) : bce_grad(o, bit ? cls_hi : cls_lo);
+                    g = g * op.cls_gain;
+                } else {
+                    g = bce_grad(o, bit ? cls_hi : cls_lo);
+                }
             }
         }
         g_out[e] = g * gscale;
     }
 }
+
+
 
 // yololoss.py:402-407: output[...,4]*=obj_mask; output[...,{0-3,5..}]*=tgt_mask; output[...,2:4]*=tgt_scale
 __global__ __launch_bounds__(256) void yolo_loss_mask_output_kernel(float* __restrict__ output,
@@ -761,8 +898,8 @@ __global__ __launch_bounds__(256) void yolo_loss_mask_output_kernel(float* __res
 
 __global__ void yolo_dense_targets_kernel(float* __restrict__ target, float* __restrict__ tgt_mask,
                                           float* __restrict__ tgt_scale, int B, int F, int A, int R, int C, int cw,
-                                          float cls_lo, float cls_hi, LossPtrs w) {
-    // one thread per (image, record slot)
+                                          float cls_lo, float cls_hi, LossPtrs w, const float* __restrict__ pos_obj) {
+    // one thread per (image, record slot); pos_obj: the records' objectness targets (obj_iou_ratio > 0) or NULL for 1
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long long)B * R) return;
     const int b = (int)(idx / R), rec = (int)(idx - (long long)b * R);
@@ -771,7 +908,7 @@ __global__ void yolo_dense_targets_kernel(float* __restrict__ target, float* __r
     const int n_ch = 5 + C;
     const float* pv = w.pos_val + (long long)idx * 5;
     float* t = target + cell * n_ch;
-    t[0] = pv[0]; t[1] = pv[1]; t[2] = pv[2]; t[3] = pv[3]; t[4] = 1.f;
+    t[0] = pv[0]; t[1] = pv[1]; t[2] = pv[2]; t[3] = pv[3]; t[4] = pos_obj ? pos_obj[idx] : 1.f;
     for (int k = 0; k < C; ++k)                                // label smoothing off: 1 and the 0 the host's memset left
         t[5 + k] = ((w.pos_cls[(long long)idx * cw + (k >> 5)] >> (k & 31)) & 1u) ? cls_hi : cls_lo;
     float* tm = tgt_mask + cell * (4 + C);
@@ -790,8 +927,6 @@ __global__ void yolo_dense_targets_kernel(float* __restrict__ target, float* __r
 // intersection passes a gradient only when the raw extent is > 0.  CIoU's alpha is a constant in the gradient.
 // fmaxf / fminf drop NaN operands: a NaN in p is carried to the result explicitly.
 constexpr float BOX_EPS = 1e-7f;
-
-struct BoxTerm { float loss, g0, g1, g2, g3; };                // g: d loss / d(px, py, log pw, log ph)
 
 template <bool GRAD>
 __device__ __forceinline__ BoxTerm box_term(int kind, float px, float py, float pw, float ph, float tx, float ty,
@@ -1933,19 +2068,25 @@ size_t y4_yolo_loss_workspace_ex(int B, int F, int A, int K, int n_classes, floa
     return loss_ws(B, F, A, K, n_classes, loss_rec_cap(K, A, iou_thresh)).total;
 }
 
+size_t y4_yolo_loss_workspace_opts(int B, int F, int A, int K, int n_classes, const y4_loss_opts* opts) {
+    if (!loss_dims_ok(B, F, A, K, n_classes) || !opts || !loss_opts_all_ok(opts)) return 0;
+    return loss_ws(B, F, A, K, n_classes, loss_rec_cap(K, A, opts->iou_thresh), opts->obj_iou_ratio > 0.f).total;
+}
+
 size_t y4_yolo_loss_workspace(int B, int F, int A, int K, int n_classes) {
     if (B <= 0 || F <= 0 || A <= 0 || K <= 0 || n_classes <= 0) return 0;
     return loss_ws(B, F, A, K, n_classes, K).total;
 }
 
-int y4_yolo_loss_fwd_ex_f32(const float* output, const float* pred, const float* labels, int K,
-                            int B, int F, int A, int n_classes, float stride, float ignore_thresh,
-                            const float* all_anchors_host, int n_all_anchors, const int* anch_mask_host,
-                            float iou_thresh, float label_smooth, float* obj_mask, double* loss_parts,
-                            void* workspace, size_t workspace_bytes, void* stream) {
-    if (!output || !pred || !labels || !obj_mask || !loss_parts || !workspace || !anch_mask_host) return Y4_ERR_NULL;
+int y4_yolo_loss_fwd_opts_f32(const float* output, const float* pred, const float* labels, int K,
+                              int B, int F, int A, int n_classes, float stride, float ignore_thresh,
+                              const float* all_anchors_host, int n_all_anchors, const int* anch_mask_host,
+                              const y4_loss_opts* opts, float* obj_mask, double* loss_parts,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    if (!output || !pred || !labels || !obj_mask || !loss_parts || !workspace || !anch_mask_host || !opts) return Y4_ERR_NULL;
     if (B <= 0 || F <= 0 || A != 3 || K <= 0 || n_classes <= 0 || (long long)A * F * F >= (1ll << 31)) return Y4_ERR_SHAPE;
-    if (!loss_opts_ok(iou_thresh, label_smooth) || (long long)B * K * A >= (1ll << 31)) return Y4_ERR_SHAPE;
+    if (!loss_opts_all_ok(opts) || (long long)B * K * A >= (1ll << 31)) return Y4_ERR_SHAPE;
+    const float iou_thresh = opts->iou_thresh, label_smooth = opts->label_smooth;
     const bool multi = iou_thresh < 1.f;
     Anchors all, masked;
     if (!fill_anchors(all, all_anchors_host, n_all_anchors)) return Y4_ERR_SHAPE;
@@ -1958,7 +2099,7 @@ int y4_yolo_loss_fwd_ex_f32(const float* output, const float* pred, const float*
     }
     fill_anchors(masked, mwh, 3);
     const int R = loss_rec_cap(K, A, iou_thresh);
-    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R, opts->obj_iou_ratio > 0.f);
     if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
     const LossPtrs w = loss_ptrs(workspace, l);
     const float cls_lo = 0.5f * label_smooth, cls_hi = 1.0f - cls_lo;      // Darknet's rule; 0 and 1 without smoothing
@@ -1978,12 +2119,34 @@ int y4_yolo_loss_fwd_ex_f32(const float* output, const float* pred, const float*
                            n_all_anchors, m0, m1, m2, masked, iou_thresh, w);
     }
     Y4_CHECK_LAUNCH();
-    hipLaunchKernelGGL(yolo_loss_dense_kernel, dim3(l.nblocks), dim3(LOSS_BLOCK), 0, st, output, pred, B, F, A, K, R,
+    if (loss_opts_any(opts)) {
+        const LossOptK op = loss_opt_k(opts, workspace, l);
+        hipLaunchKernelGGL((yolo_loss_dense_kernel<true, LossOptK>), dim3(l.nblocks), dim3(LOSS_BLOCK), 0, st, output, pred, B, F, A, K,
+                           R, n_classes, l.cw, ignore_thresh, cls_lo, cls_hi, obj_mask, w, op);
+        Y4_CHECK_LAUNCH();
+        hipLaunchKernelGGL((yolo_loss_final_kernel<true, LossOptK>), dim3(1), dim3(256), 0, st, w.partials, l.nblocks,
+                           loss_parts, op);
+        Y4_CHECK_LAUNCH();
+        return Y4_OK;
+    }
+    // the defaults: the instances in which the options do not exist
+    hipLaunchKernelGGL(yolo_loss_dense_kernel<false>, dim3(l.nblocks), dim3(LOSS_BLOCK), 0, st, output, pred, B, F, A, K, R,
                        n_classes, l.cw, ignore_thresh, cls_lo, cls_hi, obj_mask, w);
     Y4_CHECK_LAUNCH();
-    hipLaunchKernelGGL(yolo_loss_final_kernel, dim3(1), dim3(256), 0, st, w.partials, l.nblocks, loss_parts);
+    hipLaunchKernelGGL(yolo_loss_final_kernel<false>, dim3(1), dim3(256), 0, st, w.partials, l.nblocks, loss_parts);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
+}
+
+int y4_yolo_loss_fwd_ex_f32(const float* output, const float* pred, const float* labels, int K,
+                            int B, int F, int A, int n_classes, float stride, float ignore_thresh,
+                            const float* all_anchors_host, int n_all_anchors, const int* anch_mask_host,
+                            float iou_thresh, float label_smooth, float* obj_mask, double* loss_parts,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    const y4_loss_opts o = loss_opts_default(iou_thresh, label_smooth);
+    return y4_yolo_loss_fwd_opts_f32(output, pred, labels, K, B, F, A, n_classes, stride, ignore_thresh, all_anchors_host,
+                                     n_all_anchors, anch_mask_host, &o, obj_mask, loss_parts, workspace, workspace_bytes,
+                                     stream);
 }
 
 int y4_yolo_loss_fwd_f32(const float* output, const float* pred, const float* labels, int K,
@@ -1996,23 +2159,40 @@ int y4_yolo_loss_fwd_f32(const float* output, const float* pred, const float* la
                                    workspace_bytes, stream);
 }
 
-int y4_yolo_loss_bwd_ex_f32(const float* output, int output_is_masked, const float* obj_mask,
-                            const float* gscale, float* g_output,
-                            int B, int F, int A, int K, int n_classes, float iou_thresh, float label_smooth,
-                            const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!output || !obj_mask || !g_output || !workspace || !gscale) return Y4_ERR_NULL;
-    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_ok(iou_thresh, label_smooth)) return Y4_ERR_SHAPE;
+int y4_yolo_loss_bwd_opts_f32(const float* output, int output_is_masked, const float* obj_mask,
+                              const float* gscale, float* g_output,
+                              int B, int F, int A, int K, int n_classes, const y4_loss_opts* opts,
+                              const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!output || !obj_mask || !g_output || !workspace || !gscale || !opts) return Y4_ERR_NULL;
+    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_all_ok(opts)) return Y4_ERR_SHAPE;
+    const float iou_thresh = opts->iou_thresh, label_smooth = opts->label_smooth;
     const int R = loss_rec_cap(K, A, iou_thresh);
-    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R, opts->obj_iou_ratio > 0.f);
     if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
     const LossPtrs w = loss_ptrs(workspace, l);
     const float cls_lo = 0.5f * label_smooth, cls_hi = 1.0f - cls_lo;
     const long long total = (long long)B * A * F * F * (5 + n_classes);
-    hipLaunchKernelGGL(yolo_loss_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, y4_stream(stream), output,
+    if (loss_opts_any(opts)) {
+        hipLaunchKernelGGL((yolo_loss_bwd_kernel<true, LossOptK>), dim3(grid_for(total)), dim3(256), 0, y4_stream(stream), output,
+                           output_is_masked, obj_mask, gscale, g_output, B, F, A, R, n_classes, l.cw, cls_lo, cls_hi, w,
+                           loss_opt_k(opts, workspace, l));
+        Y4_CHECK_LAUNCH();
+        return Y4_OK;
+    }
+    hipLaunchKernelGGL(yolo_loss_bwd_kernel<false>, dim3(grid_for(total)), dim3(256), 0, y4_stream(stream), output,
                        output_is_masked, obj_mask,
                        gscale, g_output, B, F, A, R, n_classes, l.cw, cls_lo, cls_hi, w);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
+}
+
+int y4_yolo_loss_bwd_ex_f32(const float* output, int output_is_masked, const float* obj_mask,
+                            const float* gscale, float* g_output,
+                            int B, int F, int A, int K, int n_classes, float iou_thresh, float label_smooth,
+                            const void* workspace, size_t workspace_bytes, void* stream) {
+    const y4_loss_opts o = loss_opts_default(iou_thresh, label_smooth);
+    return y4_yolo_loss_bwd_opts_f32(output, output_is_masked, obj_mask, gscale, g_output, B, F, A, K, n_classes, &o,
+                                     workspace, workspace_bytes, stream);
 }
 
 int y4_yolo_loss_bwd_f32(const float* output, int output_is_masked, const float* obj_mask,
@@ -2044,13 +2224,14 @@ int y4_yolo_loss_mask_output_f32(float* output, const float* obj_mask, int B, in
     return y4_yolo_loss_mask_output_ex_f32(output, obj_mask, B, F, A, K, n_classes, 1.0f, workspace, workspace_bytes, stream);
 }
 
-int y4_yolo_loss_dense_targets_ex_f32(float* target, float* tgt_mask, float* tgt_scale,
-                                      int B, int F, int A, int K, int n_classes, float iou_thresh, float label_smooth,
-                                      const void* workspace, size_t workspace_bytes, void* stream) {
-    if (!target || !tgt_mask || !tgt_scale || !workspace) return Y4_ERR_NULL;
-    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_ok(iou_thresh, label_smooth)) return Y4_ERR_SHAPE;
+int y4_yolo_loss_dense_targets_opts_f32(float* target, float* tgt_mask, float* tgt_scale,
+                                        int B, int F, int A, int K, int n_classes, const y4_loss_opts* opts,
+                                        const void* workspace, size_t workspace_bytes, void* stream) {
+    if (!target || !tgt_mask || !tgt_scale || !workspace || !opts) return Y4_ERR_NULL;
+    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_all_ok(opts)) return Y4_ERR_SHAPE;
+    const float iou_thresh = opts->iou_thresh, label_smooth = opts->label_smooth;
     const int R = loss_rec_cap(K, A, iou_thresh);
-    const LossWs l = loss_ws(B, F, A, K, n_classes, R);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R, opts->obj_iou_ratio > 0.f);
     if (workspace_bytes < l.total) return Y4_ERR_WORKSPACE;
     const LossPtrs w = loss_ptrs(workspace, l);
     const float cls_lo = 0.5f * label_smooth, cls_hi = 1.0f - cls_lo;
@@ -2061,9 +2242,18 @@ int y4_yolo_loss_dense_targets_ex_f32(float* target, float* tgt_mask, float* tgt
     if (hipMemsetAsync(tgt_scale, 0, cells * 2 * 4, st) != hipSuccess) return Y4_ERR_LAUNCH;
     const long long slots = (long long)B * R;
     hipLaunchKernelGGL(yolo_dense_targets_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, target, tgt_mask,
-                       tgt_scale, B, F, A, R, n_classes, l.cw, cls_lo, cls_hi, w);
+                       tgt_scale, B, F, A, R, n_classes, l.cw, cls_lo, cls_hi, w,
+                       (const float*)loss_opt_k(opts, workspace, l).pos_obj);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
+}
+
+int y4_yolo_loss_dense_targets_ex_f32(float* target, float* tgt_mask, float* tgt_scale,
+                                      int B, int F, int A, int K, int n_classes, float iou_thresh, float label_smooth,
+                                      const void* workspace, size_t workspace_bytes, void* stream) {
+    const y4_loss_opts o = loss_opts_default(iou_thresh, label_smooth);
+    return y4_yolo_loss_dense_targets_opts_f32(target, tgt_mask, tgt_scale, B, F, A, K, n_classes, &o, workspace,
+                                               workspace_bytes, stream);
 }
 
 int y4_yolo_loss_dense_targets_f32(float* target, float* tgt_mask, float* tgt_scale,

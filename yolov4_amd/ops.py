@@ -16,7 +16,7 @@ import os
 
 import torch
 
-from ._lib import ACT_IDS, Y4Error, check, float_array, int_array, lib
+from ._lib import ACT_IDS, FOCAL_TERMS, LossOpts, Y4Error, check, float_array, int_array, lib
 
 CL = torch.channels_last
 
@@ -1886,19 +1886,60 @@ def check_loss_options(iou_thresh, label_smooth):
     return iou_thresh, label_smooth
 
 
+def check_focal_options(focal_gamma=0.0, focal_alpha=0.25, focal_terms='obj+cls', obj_iou_ratio=0.0, obj_gain=1.0,
+                        cls_gain=1.0, box_loss='ciou'):
+    """(focal_gamma, focal_alpha, focal_terms, obj_iou_ratio, obj_gain, cls_gain) checked, the numbers as floats;
+    ValueError for anything out of its domain (NaN included), before anything touches a GPU.  focal_alpha and
+    focal_terms are not looked at with focal_gamma = 0.  obj_iou_ratio > 0 needs an IoU-family box_loss: the measure is
+    the configured box loss's own X, and 'mse' has none."""
+    g, a, r = float(focal_gamma), float(focal_alpha), float(obj_iou_ratio)
+    if not (g == 0.0 or 0.5 <= g <= 5.0):
+        raise ValueError(f'focal_gamma must be 0 (off) or in [0.5, 5], got {focal_gamma!r}')
+    if g > 0.0:
+        if not 0.0 <= a < 1.0:
+            raise ValueError(f'focal_alpha must be 0 (no class balance) or in (0, 1), got {focal_alpha!r}')
+        if focal_terms not in FOCAL_TERMS:
+            raise ValueError(f'focal_terms must be one of {sorted(FOCAL_TERMS)}, got {focal_terms!r}')
+    if not 0.0 <= r <= 1.0:
+        raise ValueError(f'obj_iou_ratio must be in [0, 1], got {obj_iou_ratio!r}')
+    if r > 0.0 and box_loss_kind(box_loss) == 0:
+        raise ValueError("obj_iou_ratio > 0 needs an IoU-family box_loss ('iou', 'giou', 'diou', 'ciou'), not 'mse'")
+    gains = []
+    for name, v in (('obj_gain', obj_gain), ('cls_gain', cls_gain)):
+        v = float(v)
+        if not 0.0 < v < float('inf'):
+            raise ValueError(f'{name} must be finite and > 0, got {v!r}')
+        gains.append(v)
+    return g, a, focal_terms, r, gains[0], gains[1]
+
+
+def loss_opts_struct(cfg):
+    """The y4_loss_opts of a layer's cfg dict (YOLOLoss._layer_cfg); every key is optional and defaults to off."""
+    iou_thresh, label_smooth = check_loss_options(cfg.get('iou_thresh', 1.0), cfg.get('label_smooth', 0.0))
+    box_loss = cfg.get('obj_iou_kind') or cfg.get('box_loss', 'mse')        # the measure of obj_iou_ratio: the box loss's
+    g, a, terms, r, og, cg = check_focal_options(cfg.get('focal_gamma', 0.0), cfg.get('focal_alpha', 0.25),
+                                                 cfg.get('focal_terms', 'obj+cls'), cfg.get('obj_iou_ratio', 0.0),
+                                                 cfg.get('obj_gain', 1.0), cfg.get('cls_gain', 1.0), box_loss)
+    kind = box_loss_kind(box_loss) or BOX_LOSS_KINDS['ciou']             # not read with obj_iou_ratio = 0
+    return LossOpts(iou_thresh, label_smooth, g, a, FOCAL_TERMS[terms] if g > 0.0 else 3, r, kind, og, cg)
+
+
 class YoloLossLayerFn(torch.autograd.Function):
     """YOLOLoss.build_target + loss terms for one layer, yolo/model/yololoss.py:118-371,385-432.  With
     cfg['box_loss'] in {'iou', 'giou', 'diou', 'ciou'} the xy / wh terms are replaced by cfg['box_gain'] * sum(1 - X)
     over the positive records (parts[0]; parts[1] = 0): two more launches on the same workspace.  Optional
     cfg['iou_thresh'] (several positive anchors per label), cfg['label_smooth'] (class targets) and cfg['scale_xy'] (the
-    layer's decode factor, for the box gradient): include/yolov4_amd.h, "YOLOv4 head options of the loss"."""
+    layer's decode factor, for the box gradient): include/yolov4_amd.h, "YOLOv4 head options of the loss".  Optional
+    cfg['focal_gamma'], ['focal_alpha'], ['focal_terms'], ['obj_iou_ratio'], ['obj_gain'], ['cls_gain']: focal loss,
+    IoU-aware objectness and the term gains (check_focal_options; include/yolov4_amd.h, y4_loss_opts)."""
 
     @staticmethod
     def forward(ctx, output, pred, labels, cfg):
         L = lib()
         box_kind = box_loss_kind(cfg.get('box_loss', 'mse'))
         box_gain = float(cfg.get('box_gain', 1.0))
-        iou_thresh, label_smooth = check_loss_options(cfg.get('iou_thresh', 1.0), cfg.get('label_smooth', 0.0))
+        opts = loss_opts_struct(cfg)                 # kept on ctx: the backward passes the same struct
+        iou_thresh, label_smooth = opts.iou_thresh, opts.label_smooth
         scale_xy = check_scale_xy(cfg.get('scale_xy', 1.0))
         _require_gpu(output, 'YOLOLoss output')
         B, A, F, _, n_ch = output.shape
@@ -1908,28 +1949,28 @@ class YoloLossLayerFn(torch.autograd.Function):
             raise Y4Error('YOLOLoss: `output` must be contiguous [B,A,F,F,5+C]')
         pred = pred.detach().contiguous()
         labels = labels.detach().to(device=output.device, dtype=torch.float32).contiguous()
-        nbytes = L.y4_yolo_loss_workspace_ex(B, F, A, K, C, iou_thresh)
+        nbytes = L.y4_yolo_loss_workspace_opts(B, F, A, K, C, ctypes.byref(opts))
         ws = _ws(nbytes, output.device)
         obj_mask = torch.empty((B, A, F, F), device=output.device, dtype=torch.float32)
         parts = torch.empty(4, device=output.device, dtype=torch.float64)
         anchors = float_array([v for wh in cfg['all_anchors'] for v in wh])
         amask = int_array(cfg['anch_mask'])
-        check(L.y4_yolo_loss_fwd_ex_f32(_ptr(output), _ptr(pred), _ptr(labels), K, B, F, A, C, float(cfg['stride']),
-                                        float(cfg['ignore_thresh']), anchors, len(cfg['all_anchors']), amask,
-                                        iou_thresh, label_smooth, _ptr(obj_mask), _ptr(parts), _ptr(ws), nbytes,
-                                        _stream()), 'yolo_loss_fwd')
+        check(L.y4_yolo_loss_fwd_opts_f32(_ptr(output), _ptr(pred), _ptr(labels), K, B, F, A, C, float(cfg['stride']),
+                                          float(cfg['ignore_thresh']), anchors, len(cfg['all_anchors']), amask,
+                                          ctypes.byref(opts), _ptr(obj_mask), _ptr(parts), _ptr(ws), nbytes,
+                                          _stream()), 'yolo_loss_fwd')
         if box_kind:
             check(L.y4_yolo_box_loss_fwd_ex_f32(_ptr(pred), box_kind, box_gain, B, F, A, K, C, iou_thresh, _ptr(parts),
                                                 _ptr(ws), nbytes, _stream()), 'yolo_box_loss_fwd')
         ctx.box = (box_kind, box_gain, pred if box_kind else None)      # the backward reads the box from pred
         ctx.meta = (B, F, A, K, C, nbytes)
-        ctx.opts = (iou_thresh, label_smooth, scale_xy)
+        ctx.opts = (iou_thresh, label_smooth, scale_xy, opts)
         ctx.ws = ws
         ctx.obj_mask = obj_mask
         ctx.output = output          # later mutated in place exactly like the reference does
         ctx.mutate = cfg.get('mutate_output', True)
         cfg['last'] = dict(obj_mask=obj_mask, parts=parts, ws=ws, nbytes=nbytes, dims=(B, F, A, K, C),
-                           iou_thresh=iou_thresh, label_smooth=label_smooth,
+                           iou_thresh=iou_thresh, label_smooth=label_smooth, opts=opts,
                            rec_cap=K * A if iou_thresh < 1.0 else K)    # record slots per image in ws
         loss = parts.sum().to(torch.float32)
         if ctx.mutate:
@@ -1943,11 +1984,11 @@ class YoloLossLayerFn(torch.autograd.Function):
     def backward(ctx, gloss):
         L = lib()
         B, F, A, K, C, nbytes = ctx.meta
-        iou_thresh, label_smooth, scale_xy = ctx.opts
+        iou_thresh, label_smooth, scale_xy, opts = ctx.opts
         g = torch.empty_like(ctx.output)
         gs = gloss.detach().to(torch.float32).reshape(1).contiguous()
-        check(L.y4_yolo_loss_bwd_ex_f32(_ptr(ctx.output), 1 if ctx.mutate else 0, _ptr(ctx.obj_mask), _ptr(gs), _ptr(g),
-                                        B, F, A, K, C, iou_thresh, label_smooth, _ptr(ctx.ws), nbytes, _stream()),
+        check(L.y4_yolo_loss_bwd_opts_f32(_ptr(ctx.output), 1 if ctx.mutate else 0, _ptr(ctx.obj_mask), _ptr(gs), _ptr(g),
+                                          B, F, A, K, C, ctypes.byref(opts), _ptr(ctx.ws), nbytes, _stream()),
               'yolo_loss_bwd')
         box_kind, box_gain, pred = ctx.box
         if box_kind:
@@ -1964,9 +2005,11 @@ def yolo_loss_dense_targets(last):
     target = torch.empty((B, A, F, F, 5 + C), device=dev, dtype=torch.float32)
     tgt_mask = torch.empty((B, A, F, F, 4 + C), device=dev, dtype=torch.float32)
     tgt_scale = torch.empty((B, A, F, F, 2), device=dev, dtype=torch.float32)
-    check(L.y4_yolo_loss_dense_targets_ex_f32(_ptr(target), _ptr(tgt_mask), _ptr(tgt_scale), B, F, A, K, C,
-                                              last.get('iou_thresh', 1.0), last.get('label_smooth', 0.0),
-                                              _ptr(last['ws']), last['nbytes'], _stream()), 'yolo_loss_dense_targets')
+    opts = last.get('opts') or LossOpts(last.get('iou_thresh', 1.0), last.get('label_smooth', 0.0), 0.0, 0.25, 3, 0.0,
+                                        BOX_LOSS_KINDS['ciou'], 1.0, 1.0)
+    check(L.y4_yolo_loss_dense_targets_opts_f32(_ptr(target), _ptr(tgt_mask), _ptr(tgt_scale), B, F, A, K, C,
+                                                ctypes.byref(opts), _ptr(last['ws']), last['nbytes'], _stream()),
+          'yolo_loss_dense_targets')
     return target, tgt_mask, tgt_scale
 
 

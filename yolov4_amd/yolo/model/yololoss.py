@@ -6,7 +6,10 @@ reference: box_loss = 'iou' | 'giou' | 'diou' | 'ciou' replaces the xy / wh term
 box_gain * sum(1 - X) over the positive cells (DESIGN.md, "IoU-family box losses");
 iou_thresh < 1 makes every anchor whose shape IoU with a label exceeds it positive (Darknet's
 iou_thresh, 0.213 in yolov4.cfg), label_smooth smooths the class BCE targets, and the model
-cfg's SCALE_X_Y reaches the box-loss gradient."""
+cfg's SCALE_X_Y reaches the box-loss gradient.  focal_gamma > 0 turns the
+objectness and / or class BCE terms into the soft-target focal loss, obj_iou_ratio > 0 trains
+objectness towards the box loss's own IoU measure, and obj_gain (one number or one per layer) /
+cls_gain weigh the two terms.  Everything is off by default."""
 from typing import Dict
 
 import numpy as np
@@ -27,10 +30,18 @@ class YOLOLoss(nn.Module):
     strides = [8, 16, 32]
 
     def __init__(self, cfg: Dict, ignore_thresh=0.7, device=None, mutate_outputs=True, box_loss='mse', box_gain=1.0,
-                 iou_thresh=1.0, label_smooth=0.0):
+                 iou_thresh=1.0, label_smooth=0.0, focal_gamma=0.0, focal_alpha=0.25, focal_terms='obj+cls',
+                 obj_iou_ratio=0.0, obj_gain=1.0, cls_gain=1.0):
         super().__init__()
         ops.box_loss_kind(box_loss)                 # ValueError for an unknown name, before anything touches a GPU
         self.iou_thresh, self.label_smooth = ops.check_loss_options(iou_thresh, label_smooth)
+        per_layer = list(obj_gain) if isinstance(obj_gain, (list, tuple)) else [obj_gain] * n_layers(cfg)
+        if len(per_layer) != n_layers(cfg):
+            raise ValueError(f'obj_gain must be one number or one per layer ({n_layers(cfg)}), got {obj_gain!r}')
+        checked = [ops.check_focal_options(focal_gamma, focal_alpha, focal_terms, obj_iou_ratio, og, cls_gain, box_loss)
+                   for og in per_layer]
+        self.focal_gamma, self.focal_alpha, self.focal_terms, self.obj_iou_ratio, _, self.cls_gain = checked[0]
+        self.obj_gain = [c[4] for c in checked]     # one per layer
         self.scale_xy = [layer_scale_xy(cfg, l) for l in range(n_layers(cfg))]
         if box_loss == 'mse' and any(s != 1.0 for s in self.scale_xy):
             # the xy BCE target is defined against the unscaled sigmoid; Darknet does not combine the two either
@@ -53,14 +64,17 @@ class YOLOLoss(nn.Module):
         return {'stride': st, 'ignore_thresh': float(np.float32(self.ignore_thresh)), 'all_anchors': grid,
                 'anch_mask': list(self.cfg['ANCHOR_MASK'][layer_no]), 'mutate_output': self.mutate_outputs,
                 'box_loss': self.box_loss, 'box_gain': self.box_gain, 'iou_thresh': self.iou_thresh,
-                'label_smooth': self.label_smooth, 'scale_xy': self.scale_xy[layer_no]}
+                'label_smooth': self.label_smooth, 'scale_xy': self.scale_xy[layer_no],
+                'focal_gamma': self.focal_gamma, 'focal_alpha': self.focal_alpha, 'focal_terms': self.focal_terms,
+                'obj_iou_ratio': self.obj_iou_ratio, 'obj_iou_kind': self.box_loss,
+                'obj_gain': self.obj_gain[layer_no], 'cls_gain': self.cls_gain}
 
     def build_target(self, output, pred, layer_no, labels):
         """Dense (target, obj_mask, tgt_mask, tgt_scale) as yololoss.py:118-371 returns them; with the options, every
         positive anchor's cell is filled and target[..., 5:] holds the smoothed class targets there."""
         cfg = self._layer_cfg(layer_no)
         cfg['mutate_output'] = False
-        cfg['box_loss'] = 'mse'                     # the dense targets do not depend on the box loss
+        cfg['box_loss'] = 'mse'                     # no box-loss launches; obj_iou_kind keeps the measure of t_obj
         ops.YoloLossLayerFn.apply(output.detach().contiguous(), pred, labels, cfg)
         target, tgt_mask, tgt_scale = ops.yolo_loss_dense_targets(cfg['last'])
         return target, cfg['last']['obj_mask'], tgt_mask, tgt_scale
