@@ -605,6 +605,29 @@ int y4_yolo_loss_dense_targets_opts_f32(float* target, float* tgt_mask, float* t
                                         int B, int F, int A, int K, int n_classes, const y4_loss_opts* opts,
                                         const void* workspace, size_t workspace_bytes, void* stream);
 
+/* Per-layer training statistics of the loss (Darknet's "Avg IOU, .5R, .75R, Class, Obj, No Obj, count" line), read from
+ * `output`, `pred`, `obj_mask` and the workspace that y4_yolo_loss_fwd_opts_f32 has just filled with the same opts.  Call
+ * it after that forward and BEFORE y4_yolo_loss_mask_output*_f32 multiplies the masks into `output`.  Two launches, no
+ * host synchronisation; twelve doubles are ADDED to stats_row (device memory, caller-owned, zeroed by the caller):
+ *    0 n_cells      B A F F
+ *    1 n_pos        cells with a record (pos_index >= 0); one record per cell, class bits OR-ed, box of the last writer
+ *    2 n_ign        cells with obj_mask == 0
+ *    3 sum_iou      sum over positive cells of X = 1 - (box loss of kind Y4_BOX_IOU on the record), the operands and bits
+ *                   of y4_yolo_box_loss_fwd with that kind, whatever box loss is configured; a NaN pred makes it NaN
+ *    4 n_iou50      positive cells with X > 0.5 (a NaN X counts as no)      5 n_iou75: X > 0.75
+ *    6 sum_obj_pos  sum of output[..., 4] over positive cells
+ *    7 sum_obj_bg   sum of output[..., 4] over cells without a record and obj_mask != 0;     8 n_bg: their number
+ *    9 sum_cls      sum over positive cells and the set class bits c of their record of output[..., 5 + c]
+ *   10 n_cls        number of those bits
+ *   11 n_top1       positive cells whose arg-max class channel (lowest index on ties) has its bit set
+ * Counts are exact integers; the sums are fp64 sums of the fp32 values in a fixed order (block partials, then one fold).
+ * Of opts only iou_thresh (the record slots) and obj_iou_ratio (the workspace size) are looked at.  `scratch`:
+ * y4_yolo_loss_stats_scratch(B, F, A) bytes of device memory, overwritten.  Errors before any launch as above. */
+size_t y4_yolo_loss_stats_scratch(int B, int F, int A);
+int y4_yolo_loss_stats_f64(const float* output, const float* pred, const float* obj_mask, int B, int F, int A, int K,
+                           int n_classes, const y4_loss_opts* opts, const void* workspace, size_t workspace_bytes,
+                           void* scratch, size_t scratch_bytes, double* stats_row, void* stream);
+
 /* Device-side prefix sums of postprocess (no host round trip between its stages):
  * y4_post_scan_i32: seg_offsets[0..n_segments] = exclusive scan of the candidate counts, clamped to `cap` (the capacity, in
  *   candidates, of the buffers the caller allocated: a too-small capacity truncates segments, it never overflows);

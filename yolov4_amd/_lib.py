@@ -113,6 +113,8 @@ PROTOTYPES = {
     'y4_yolo_loss_fwd_opts_f32': (I, [P, P, P, I, I, I, I, I, F, F, P, I, P, P, P, P, P, Z, P]),
     'y4_yolo_loss_bwd_opts_f32': (I, [P, I, P, P, P, I, I, I, I, I, P, P, Z, P]),
     'y4_yolo_loss_dense_targets_opts_f32': (I, [P, P, P, I, I, I, I, I, P, P, Z, P]),
+    'y4_yolo_loss_stats_scratch': (Z, [I, I, I]),
+    'y4_yolo_loss_stats_f64': (I, [P, P, P, I, I, I, I, I, P, P, Z, P, Z, P, P]),
     'y4_post_count_f32': (I, [P, I, L, I, F, I, P, P]),
     'y4_post_scan_i32': (I, [P, I, L, P, P, P]),
     'y4_post_compact_f32': (I, [P, P, P, I, I, P, P, P, P]),

@@ -1064,6 +1064,100 @@ __global__ __launch_bounds__(256) void yolo_box_loss_bwd_kernel(const float* __r
     g[3] = (r.g3 * gain) * gscale;
 }
 
+// ------------------------------------------------------------------------------------ training statistics of the loss
+// Darknet's per-layer line (count, Avg IOU, .5R, .75R, Obj, No Obj, Class) from what the loss forward left behind: one
+// thread per cell, as in yolo_loss_dense_kernel (channel 4 of the 5 + C row; a positive cell also walks its class
+// channels).  X is t_obj's expression with the kind fixed to IoU.  Eleven block partials ([nblocks, 11] doubles: the
+// seven counts are exact integers there), folded in a fixed order by the second kernel, which ADDS them to the caller's
+// row: the sums are bit-reproducible for a given shape.  Row entry 0 (n_cells) is added by the fold.
+constexpr int STATS_N = 12;
+constexpr int STATS_P = STATS_N - 1;                           // partial q holds row entry q + 1
+__global__ __launch_bounds__(LOSS_BLOCK) void yolo_loss_stats_kernel(
+    const float* __restrict__ output, const float* __restrict__ pred, const float* __restrict__ obj_mask, int B, int F,
+    int A, int R, int C, int cw, LossPtrs w, double* __restrict__ partials) {
+    __shared__ double red[STATS_P][LOSS_BLOCK / 64];
+    const long long cells = (long long)B * A * F * F;
+    const long long cell = (long long)blockIdx.x * LOSS_BLOCK + threadIdx.x;
+    const int n_ch = 5 + C;
+    // q + 1: 1 n_pos, 2 n_ign, 3 sum_iou, 4 n_iou50, 5 n_iou75, 6 sum_obj_pos, 7 sum_obj_bg, 8 n_bg, 9 sum_cls, 10 n_cls,
+    // 11 n_top1
+    double v[STATS_P];
+#pragma unroll
+    for (int q = 0; q < STATS_P; ++q) v[q] = 0.0;
+    if (cell < cells) {
+        const int per_img = A * F * F;
+        const int b = (int)(cell / per_img);
+        const int rec = w.pos_index[cell];
+        const float m = obj_mask[cell];
+        const float* o = output + cell * n_ch;
+        const float obj = o[4];
+        if (m == 0.f) v[1] = 1.0;
+        if (rec >= 0) {
+            const int c = (int)(cell - (long long)b * per_img);
+            const float fi = (float)(c % F), fj = (float)((c / F) % F);
+            const long long s = (long long)b * R + rec;
+            const float* tb = w.pos_box + s * 4;
+            const float px = pred[cell * 4], py = pred[cell * 4 + 1], pw = pred[cell * 4 + 2], ph = pred[cell * 4 + 3];
+            const float x = 1.0f - box_term<false>(Y4_BOX_IOU, px - fi, py - fj, pw, ph, tb[0] - fi, tb[1] - fj, tb[2],
+                                                   tb[3]).loss;
+            v[0] = 1.0;
+            v[2] = (double)x;                                   // a NaN pred: NaN here, and neither comparison holds
+            if (x > 0.5f) v[3] = 1.0;
+            if (x > 0.75f) v[4] = 1.0;
+            v[5] = (double)obj;
+            const unsigned* pc = w.pos_cls + s * cw;
+            double sc = 0.0;
+            int nc = 0, top = 0;
+            float best = o[5];
+            for (int k = 0; k < C; ++k) {
+                const float p = o[5 + k];
+                if ((pc[k >> 5] >> (k & 31)) & 1u) { sc += (double)p; ++nc; }
+                if (p > best) { best = p; top = k; }            // strict: the lowest index wins a tie
+            }
+            v[8] = sc;
+            v[9] = (double)nc;
+            if ((pc[top >> 5] >> (top & 31)) & 1u) v[10] = 1.0;
+        } else if (m != 0.f) {
+            v[6] = (double)obj;
+            v[7] = 1.0;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < STATS_P; ++q) {
+        double r = v[q];
+        for (int off = 32; off > 0; off >>= 1) r += __shfl_down(r, off, 64);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < STATS_P) {
+        double r = 0;
+        for (int k = 0; k < LOSS_BLOCK / 64; ++k) r += red[threadIdx.x][k];
+        partials[(long long)blockIdx.x * STATS_P + threadIdx.x] = r;
+    }
+}
+
+__global__ __launch_bounds__(256) void yolo_loss_stats_fold_kernel(const double* __restrict__ partials, int nblocks,
+                                                                   double n_cells, double* __restrict__ row) {
+    __shared__ double red[STATS_P][256];
+    double v[STATS_P];
+#pragma unroll
+    for (int q = 0; q < STATS_P; ++q) v[q] = 0.0;
+    for (int i = threadIdx.x; i < nblocks; i += 256)
+#pragma unroll
+        for (int q = 0; q < STATS_P; ++q) v[q] += partials[(long long)i * STATS_P + q];
+#pragma unroll
+    for (int q = 0; q < STATS_P; ++q) red[q][threadIdx.x] = v[q];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s)
+#pragma unroll
+            for (int q = 0; q < STATS_P; ++q) red[q][threadIdx.x] += red[q][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < STATS_P) row[1 + threadIdx.x] += red[threadIdx.x][0];
+    else if (threadIdx.x == STATS_P) row[0] += n_cells;
+}
+
 // ------------------------------------------------------------------------------------ postprocess
 // The prediction rows are [5 + C] floats (340 B at C = 80): one thread per row reads 4 B from 64 different lines per
 // load (measured: 25x the tensor's bytes on the fabric, 276 GB/s).  The tiled forms below copy POST_ROWS consecutive rows
@@ -2215,6 +2309,32 @@ int y4_yolo_loss_mask_output_ex_f32(float* output, const float* obj_mask, int B,
     const long long total = (long long)B * A * F * F * (5 + n_classes);
     hipLaunchKernelGGL(yolo_loss_mask_output_kernel, dim3(grid_for(total)), dim3(256), 0, y4_stream(stream), output,
                        obj_mask, B, F, A, R, n_classes, w);
+    Y4_CHECK_LAUNCH();
+    return Y4_OK;
+}
+
+size_t y4_yolo_loss_stats_scratch(int B, int F, int A) {
+    if (B <= 0 || F <= 0 || A <= 0) return 0;
+    const long long cells = (long long)B * A * F * F;
+    return (size_t)((cells + LOSS_BLOCK - 1) / LOSS_BLOCK) * STATS_P * sizeof(double);
+}
+
+int y4_yolo_loss_stats_f64(const float* output, const float* pred, const float* obj_mask, int B, int F, int A, int K,
+                           int n_classes, const y4_loss_opts* opts, const void* workspace, size_t workspace_bytes,
+                           void* scratch, size_t scratch_bytes, double* stats_row, void* stream) {
+    if (!output || !pred || !obj_mask || !opts || !workspace || !scratch || !stats_row) return Y4_ERR_NULL;
+    if (!loss_dims_ok(B, F, A, K, n_classes) || !loss_opts_all_ok(opts)) return Y4_ERR_SHAPE;
+    const int R = loss_rec_cap(K, A, opts->iou_thresh);
+    const LossWs l = loss_ws(B, F, A, K, n_classes, R, opts->obj_iou_ratio > 0.f);
+    if (workspace_bytes < l.total || scratch_bytes < y4_yolo_loss_stats_scratch(B, F, A)) return Y4_ERR_WORKSPACE;
+    const LossPtrs w = loss_ptrs(workspace, l);
+    double* partials = static_cast<double*>(scratch);
+    hipStream_t st = y4_stream(stream);
+    hipLaunchKernelGGL(yolo_loss_stats_kernel, dim3(l.nblocks), dim3(LOSS_BLOCK), 0, st, output, pred, obj_mask, B, F, A, R,
+                       n_classes, l.cw, w, partials);
+    Y4_CHECK_LAUNCH();
+    hipLaunchKernelGGL(yolo_loss_stats_fold_kernel, dim3(1), dim3(256), 0, st, partials, l.nblocks,
+                       (double)((long long)B * A * F * F), stats_row);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }

@@ -166,6 +166,12 @@ def build_parser():
     ap.add_argument('--conf-thre', type=float, default=-0.1)
     ap.add_argument('--nms-thre', type=float, default=-0.1)
     ap.add_argument('--batch', type=int, default=8)
+    add_inference_args(ap)
+    return ap
+
+
+def add_inference_args(ap):
+    """The NMS, letterbox and test-time-augmentation flags, shared with yolov4_amd.val"""
     # NMS options: a flag that is given overrides the cfg's TEST.NMS_METRIC / NMS_SOFT / NMS_SIGMA / NMS_AGNOSTIC / MAX_DET
     ap.add_argument('--nms-metric', choices=['iou', 'diou'], default=None)
     ap.add_argument('--soft-nms', choices=['none', 'linear', 'gaussian'], default=None)
@@ -179,7 +185,6 @@ def build_parser():
     ap.add_argument('--tta-scales', default=None, help='comma-separated, e.g. 1,0.83,0.67')
     ap.add_argument('--tta-flips', default=None, help='comma-separated 0/1, one per scale, e.g. 0,1,0')
     ap.add_argument('--tta-merge', choices=['nms', 'wbf'], default=None)
-    return ap
 
 
 def letterbox_from_args(args, cfg):

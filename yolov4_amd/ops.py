@@ -1931,7 +1931,9 @@ class YoloLossLayerFn(torch.autograd.Function):
     cfg['iou_thresh'] (several positive anchors per label), cfg['label_smooth'] (class targets) and cfg['scale_xy'] (the
     layer's decode factor, for the box gradient): include/yolov4_amd.h, "YOLOv4 head options of the loss".  Optional
     cfg['focal_gamma'], ['focal_alpha'], ['focal_terms'], ['obj_iou_ratio'], ['obj_gain'], ['cls_gain']: focal loss,
-    IoU-aware objectness and the term gains (check_focal_options; include/yolov4_amd.h, y4_loss_opts)."""
+    IoU-aware objectness and the term gains (check_focal_options; include/yolov4_amd.h, y4_loss_opts).  Optional
+    cfg['stats']: a float64 [12] device row that the layer's training statistics are added to (y4_yolo_loss_stats_f64,
+    DESIGN.md section 24); without the key nothing more is launched."""
 
     @staticmethod
     def forward(ctx, output, pred, labels, cfg):
@@ -1973,6 +1975,17 @@ class YoloLossLayerFn(torch.autograd.Function):
                            iou_thresh=iou_thresh, label_smooth=label_smooth, opts=opts,
                            rec_cap=K * A if iou_thresh < 1.0 else K)    # record slots per image in ws
         loss = parts.sum().to(torch.float32)
+        stats_row = cfg.get('stats')
+        if stats_row is not None:
+            # before the masks go into `output`: the statistics read the layer's own outputs (two launches, no sync)
+            if stats_row.dtype != torch.float64 or stats_row.numel() != 12 or not stats_row.is_contiguous() \
+                    or stats_row.device != output.device:
+                raise Y4Error('YOLOLoss: cfg["stats"] must be a contiguous float64 [12] row on the device of `output`')
+            sbytes = L.y4_yolo_loss_stats_scratch(B, F, A)
+            scratch = _ws(sbytes, output.device)
+            check(L.y4_yolo_loss_stats_f64(_ptr(output), _ptr(pred), _ptr(obj_mask), B, F, A, K, C, ctypes.byref(opts),
+                                           _ptr(ws), nbytes, _ptr(scratch), sbytes, _ptr(stats_row), _stream()),
+                  'yolo_loss_stats')
         if ctx.mutate:
             # side effect of yololoss.py:402-407 on outputs[*]['output']; done through the raw pointer,
             # the backward kernel is told that the w/h channels already carry the scale factor

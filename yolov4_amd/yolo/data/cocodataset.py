@@ -137,6 +137,8 @@ class COCOBatchLoader(object):
     per sample, every draw from `random.Random` seeded with (seed, epoch, batch): the same seed gives the same batches.
     shuffle permutes the images per epoch (`set_epoch`); rank / world_size take every world_size-th image of that order.
     Host work (file reads, Huffman decoding on `workers` threads, at most 16) runs one batch ahead of the device work.
+    multiscale (a MultiScale, yolo/data/multiscale.py; training only): batch b of epoch e is made at
+    multiscale.size_at(e, b) instead of dataset.get_img_size(); `last_img_size` is the S of the batch last yielded.
 
     Validation with letterbox = 'square' | 'rect' (None: the reference's stretch to S x S): the input is `letterbox_batch`'s
     [B, 3, Hc, Wc], labels are mapped onto the canvas, img_info rows are [h, w, nh, nw, img_id, index] and target['pad'] holds B
@@ -144,11 +146,15 @@ class COCOBatchLoader(object):
     the annotation file; no image is read for it) so that a batch's canvas is tight."""
 
     def __init__(self, dataset, batch_size, cfg, shuffle=False, seed=0, workers=8, rank=0, world_size=1, fallback=None,
-                 letterbox=None):
+                 letterbox=None, multiscale=None):
         assert batch_size >= 1 and 0 <= rank < world_size
         self.letterbox = letterbox_mode(letterbox)
         if self.letterbox is not None and dataset.is_train:
             raise ValueError('letterbox is an inference option: the training pipeline stays square')
+        if multiscale is not None and not dataset.is_train:
+            raise ValueError('multiscale is a training option: validation runs at the size of its dataset')
+        self.multiscale = multiscale
+        self.last_img_size = None                           # S of the batch last yielded
         self.dataset, self.batch_size, self.cfg = dataset, int(batch_size), cfg
         self.shuffle, self.seed, self.epoch = bool(shuffle), int(seed), 0
         self.workers = max(1, min(int(workers), MAX_WORKERS))
@@ -215,6 +221,8 @@ class COCOBatchLoader(object):
                 if b + 1 < n:
                     pending = ahead.submit(self._host_batch, order, b + 1, pool)
                 S = int(ds.get_img_size())                  # per batch: set_img_size() between batches takes effect
+                if self.multiscale is not None:
+                    S = int(self.multiscale.size_at(self.epoch, b))
                 pad = None
                 imgs = decode_entropy_batch(hb)
                 at, items = 0, []
@@ -250,4 +258,5 @@ class COCOBatchLoader(object):
                 target = {'padded_labels': labels, 'img_info': info}
                 if pad is not None:
                     target['pad'] = pad                     # letterboxed input: B rows of (top, left)
+                self.last_img_size = S
                 yield x, target

@@ -76,9 +76,24 @@ def train_step(cfg, model, criterion, optimizer, input, target, device=None, ste
     return loss
 
 
-def train(args, cfg, train_loader, model, criterion, optimizer, device=None, epoch=0, log=None, ema=None):
+def stats_lines(summary):
+    """One line per layer of YOLOLoss.stats_summary(), Darknet's per-layer report."""
+    return [f"  L{l}: count {m['count']}  avg_iou {m['avg_iou']:.4f}  .5R {m['r50']:.4f}  .75R {m['r75']:.4f}  "
+            f"obj {m['obj']:.4f}  no_obj {m['no_obj']:.6f}  cls {m['cls']:.4f}  top1 {m['top1']:.4f}  ign {m['ignored']}"
+            for l, m in enumerate(summary)]
+
+
+def train(args, cfg, train_loader, model, criterion, optimizer, device=None, epoch=0, log=None, ema=None, img_size=None,
+          stats=None):
     """build.py:41-107.  `log`: optional callable(str) (the reference logs through its rank-0 logger); `ema`: optional
-    ModelEMA handed to every train_step."""
+    ModelEMA handed to every train_step.  img_size: True ends the log line in the reference's `ImgSize: SxS` (S is the
+    loader's last_img_size); None does so exactly when the loader carries a multi-scale schedule.  stats: True prints one
+    line per layer of criterion.stats_summary() after the log line and resets the statistics; None does so exactly when
+    the criterion was built with stats=True.  With neither, the line is what it always was."""
+    if img_size is None:
+        img_size = getattr(train_loader, 'multiscale', None) is not None
+    if stats is None:
+        stats = bool(getattr(criterion, 'stats_on', False))
     batch_time, losses = AverageMeter(), AverageMeter()
     model.train()
     end = time.time()
@@ -97,9 +112,18 @@ def train(args, cfg, train_loader, model, criterion, optimizer, device=None, epo
             end = time.time()
             if log is not None:
                 bs = float(cfg['DATA']['BATCH_SIZE'])
-                log(f'Epoch: [{epoch + 1}][{i + 1}/{n}]\tTime {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
-                    f'Speed {world * bs / batch_time.val:.3f} ({world * bs / batch_time.avg:.3f})\t'
-                    f"Lr {optimizer.param_groups[0]['lr']:.8f}\tLoss {losses.val:.10f} ({losses.avg:.4f})")
+                line = (f'Epoch: [{epoch + 1}][{i + 1}/{n}]\tTime {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
+                        f'Speed {world * bs / batch_time.val:.3f} ({world * bs / batch_time.avg:.3f})\t'
+                        f"Lr {optimizer.param_groups[0]['lr']:.8f}\tLoss {losses.val:.10f} ({losses.avg:.4f})")
+                if img_size:
+                    S = getattr(train_loader, 'last_img_size', None) or input.shape[-1]
+                    line += f'\tImgSize: {S}x{S}'
+                log(line)
+                if stats:
+                    for extra in stats_lines(criterion.stats_summary()):
+                        log(extra)
+            if stats:
+                criterion.reset_stats()                     # the loss is synchronised here: the summary costs no new wait
     return losses.avg
 
 

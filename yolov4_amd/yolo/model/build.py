@@ -33,4 +33,5 @@ def build_criterion(cfg: Dict, device=None):
                     label_smooth=float(crit.get('LABEL_SMOOTH', 0.0)),
                     focal_gamma=float(crit.get('FOCAL_GAMMA', 0.0)), focal_alpha=float(crit.get('FOCAL_ALPHA', 0.25)),
                     focal_terms=crit.get('FOCAL_TERMS', 'obj+cls'), obj_iou_ratio=float(crit.get('OBJ_IOU_RATIO', 0.0)),
-                    obj_gain=crit.get('OBJ_GAIN', 1.0), cls_gain=float(crit.get('CLS_GAIN', 1.0))).to(device)
+                    obj_gain=crit.get('OBJ_GAIN', 1.0), cls_gain=float(crit.get('CLS_GAIN', 1.0)),
+                    stats=bool(crit.get('STATS', False))).to(device)

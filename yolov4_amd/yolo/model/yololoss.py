@@ -9,7 +9,10 @@ iou_thresh, 0.213 in yolov4.cfg), label_smooth smooths the class BCE targets, an
 cfg's SCALE_X_Y reaches the box-loss gradient.  focal_gamma > 0 turns the
 objectness and / or class BCE terms into the soft-target focal loss, obj_iou_ratio > 0 trains
 objectness towards the box loss's own IoU measure, and obj_gain (one number or one per layer) /
-cls_gain weigh the two terms.  Everything is off by default."""
+cls_gain weigh the two terms.  stats=True adds per-layer training statistics (positives, their
+mean IoU and recall at 0.5 / 0.75, objectness on positives and background, class confidence) to a device tensor as
+the loss runs.  Everything is off by default."""
+import math
 from typing import Dict
 
 import numpy as np
@@ -26,12 +29,19 @@ def bboxes_iou(bboxes_a, bboxes_b, xyxy=True):
     return ops.bboxes_iou_raw(bboxes_a, bboxes_b, xyxy)
 
 
+# the columns of YOLOLoss.stats, y4_yolo_loss_stats_f64's row (include/yolov4_amd.h)
+STATS_ROWS = ('n_cells', 'n_pos', 'n_ign', 'sum_iou', 'n_iou50', 'n_iou75', 'sum_obj_pos', 'sum_obj_bg', 'n_bg', 'sum_cls',
+              'n_cls', 'n_top1')
+
+
 class YOLOLoss(nn.Module):
     strides = [8, 16, 32]
 
     def __init__(self, cfg: Dict, ignore_thresh=0.7, device=None, mutate_outputs=True, box_loss='mse', box_gain=1.0,
-                 iou_thresh=1.0, label_smooth=0.0, focal_gamma=0.0, focal_alpha=0.25, focal_terms='obj+cls',
+                 iou_thresh=1.0, stats=False, label_smooth=0.0, focal_gamma=0.0, focal_alpha=0.25, focal_terms='obj+cls',
                  obj_iou_ratio=0.0, obj_gain=1.0, cls_gain=1.0):
+        # stats sits before label_smooth because the keywords from label_smooth on are a pinned list
+        # (tests/test_lossopt_cases.py); every caller passes these by name
         super().__init__()
         ops.box_loss_kind(box_loss)                 # ValueError for an unknown name, before anything touches a GPU
         self.iou_thresh, self.label_smooth = ops.check_loss_options(iou_thresh, label_smooth)
@@ -56,6 +66,9 @@ class YOLOLoss(nn.Module):
         # yololoss.py:402-407 multiplies the masks into outputs[*]['output'] in place; kept by default
         self.mutate_outputs = mutate_outputs
         self.last = [None] * n_layers(cfg)
+        # [n_layers, 12] float64 on the device, created by the first forward (the device is the outputs'); None when off
+        self.stats_on = bool(stats)
+        self.stats = None
 
     def _layer_cfg(self, layer_no):
         st = layer_strides(self.cfg, self.strides)[layer_no]
@@ -79,6 +92,32 @@ class YOLOLoss(nn.Module):
         target, tgt_mask, tgt_scale = ops.yolo_loss_dense_targets(cfg['last'])
         return target, cfg['last']['obj_mask'], tgt_mask, tgt_scale
 
+    def reset_stats(self):
+        """Zero the accumulated statistics on the device (no synchronisation)."""
+        if self.stats is not None:
+            self.stats.zero_()
+
+    def stats_summary(self):
+        """One dict per layer of what has accumulated since the last reset_stats(): count, avg_iou, r50, r75, obj,
+        no_obj, cls, top1, ignored.  The one place that synchronises; a ratio with a zero denominator is nan."""
+        if self.stats is None:
+            rows = [[0.0] * len(STATS_ROWS)] * n_layers(self.cfg) if self.stats_on else []
+        else:
+            rows = self.stats.cpu().tolist()
+
+        def ratio(a, b):
+            return a / b if b else math.nan
+
+        out = []
+        for r in rows:
+            s = dict(zip(STATS_ROWS, r))
+            out.append({'count': int(s['n_pos']), 'avg_iou': ratio(s['sum_iou'], s['n_pos']),
+                        'r50': ratio(s['n_iou50'], s['n_pos']), 'r75': ratio(s['n_iou75'], s['n_pos']),
+                        'obj': ratio(s['sum_obj_pos'], s['n_pos']), 'no_obj': ratio(s['sum_obj_bg'], s['n_bg']),
+                        'cls': ratio(s['sum_cls'], s['n_cls']), 'top1': ratio(s['n_top1'], s['n_pos']),
+                        'ignored': int(s['n_ign'])})
+        return out
+
     def forward(self, outputs, targets):
         assert isinstance(outputs, list)
         assert isinstance(targets, dict)
@@ -88,6 +127,11 @@ class YOLOLoss(nn.Module):
             assert isinstance(od, dict)
             layer_no = od['layer_no']
             cfg = self._layer_cfg(layer_no)
+            if self.stats_on:
+                if self.stats is None or self.stats.device != od['output'].device:
+                    self.stats = torch.zeros((n_layers(self.cfg), len(STATS_ROWS)), dtype=torch.float64,
+                                             device=od['output'].device)
+                cfg['stats'] = self.stats[layer_no]
             loss = ops.YoloLossLayerFn.apply(od['output'], od['pred'], labels, cfg)
             self.last[layer_no] = cfg['last']
             total = loss if total is None else total + loss
