@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """The IoU-family box losses (IoU / GIoU / DIoU / CIoU) restated in numpy, and the seeded inputs of their tests
 (tests/test_boxloss_cases.py checks the restatement and the inputs without a GPU, tests/test_gpu_boxloss.py feeds the
-inputs to the kernels of csrc/yolo_head.hip).
+inputs to the kernels of csrc/yolo_loss.hip).
 
 `box_eval` is written once and evaluated in the dtype of its inputs: in float64 it is the reference, in float32 (every
 operation rounded, absolute grid coordinates) it is the yardstick of the tolerance: a kernel may be BOX_FACTOR times as

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """NumPy float32 restatements of the test-time-augmentation kernels (csrc/tta.hip: view, merge) and of weighted box fusion
-(csrc/yolo_head.hip: post_wbf_kernel), DESIGN.md section 22, and the inputs of their tests.
+(csrc/postprocess.hip: post_wbf_kernel), DESIGN.md section 22, and the inputs of their tests.
 
 Every step is one float32 operation in the documented order (NumPy's float32 + - * / are correctly rounded, like the
 kernels', which are built without fma contraction), so the kernels are compared bit for bit: rows, order and every float.

@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """The YOLOv4 head options -- scale_x_y, several positive anchors per label (iou_thresh), class label smoothing --
 restated in numpy, and the seeded inputs of their tests (tests/test_headopt_cases.py checks the restatement and the
-inputs without a GPU, tests/test_gpu_headopt.py feeds the inputs to the kernels of csrc/yolo_head.hip).
+inputs without a GPU, tests/test_gpu_headopt.py feeds the inputs to the kernels of csrc/yolo_decode.hip and csrc/yolo_loss.hip).
 
 The rules (include/yolov4_amd.h):
   scale_x_y   s fp32 in [1, 2], h = (s - 1) * 0.5f in fp32: pred centre = ((sigma * s) - h) + cell, `output` keeps sigma;

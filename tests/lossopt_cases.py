@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """Focal loss, IoU-aware objectness and the objectness / class gains of the detection loss, restated in numpy, and the
 option sets and inputs of their tests (tests/test_lossopt_cases.py checks the restatement and the inputs without a GPU,
-tests/test_gpu_lossopt.py feeds them to the kernels of csrc/yolo_head.hip).
+tests/test_gpu_lossopt.py feeds them to the kernels of csrc/yolo_loss.hip).
 
 The rules (include/yolov4_amd.h, y4_loss_opts), with o the value in `output`, t the element's
 target, bce / bce_grad the terms of headopt_cases:

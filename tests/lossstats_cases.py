@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """Per-layer training statistics of the detection loss (y4_yolo_loss_stats_f64), restated in
 numpy, and the inputs of their tests (tests/test_lossstats_cases.py checks the restatement and the inputs without a GPU,
-tests/test_gpu_lossstats.py feeds them to the kernel of csrc/yolo_head.hip).
+tests/test_gpu_lossstats.py feeds them to the kernel of csrc/yolo_loss.hip).
 
 The restatement stands on what headopt_cases / lossopt_cases.loss_ref already restate exactly: the positive set (one
 record per cell, class bits OR-ed, box of the last writer), the cells and the ignore mask.  X, the plain IoU of a

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""The IoU-family box losses of csrc/yolo_head.hip (y4_yolo_box_loss_fwd/bwd_f32) against the float64 restatement of
+"""The IoU-family box losses of csrc/yolo_loss.hip (y4_yolo_box_loss_fwd/bwd_f32) against the float64 restatement of
 tests/boxloss_cases.py: through the C ABI on planted boxes (equal, disjoint, nested both ways, 1:40 and 40:1, touching,
 1e-3 cells wide) for every kind, layer, class count and label count on both sides of the 64-label wave kernel, and
 through YOLOLayer + YOLOLoss down to the gradient of the logits.

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
-"""The head, loss, IoU and NMS kernels of csrc/yolo_head.hip, each driven through the C ABI at the sizes where the
-host picks another kernel or a kernel takes another branch: pitch and alignment of the decode, label counts on both
+"""The head, loss, IoU and NMS kernels of csrc/yolo_decode.hip, yolo_loss.hip and postprocess.hip, each driven through the
+C ABI at the sizes where the host picks another kernel or a kernel takes another branch: pitch and alignment of the decode, label counts on both
 sides of the 64-label wave kernel, class counts on both sides of a 32-bit mask word, NMS chunk seams, segments above the
 LDS sort limit, tiles of the candidate count that span several images, and logits that saturate the fp32 sigmoid.
 

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
-"""The YOLOv4 head options of csrc/yolo_head.hip -- scale_x_y in the three decodes, several positive anchors per label
-(iou_thresh), class label smoothing, and scale_x_y in the box-loss gradient -- through the C ABI (the *_ex entries)
+"""The YOLOv4 head options of csrc/yolo_decode.hip and csrc/yolo_loss.hip -- scale_x_y in the three decodes, several
+positive anchors per label (iou_thresh), class label smoothing, and scale_x_y in the box-loss gradient -- through the C ABI (the *_ex entries)
 against the float64 restatement of tests/headopt_cases.py, then through YOLOLayer + YOLOLoss and through YOLOv4.
 
 With the options off the new entries must give the bits of the entries they generalise.  tests/test_headopt_cases.py

@@ -228,7 +228,7 @@ def test_rect_decode_against_fp64(dev, case, scale):
     on either side of the buffer untouched.
 
     At scale 1.2 the centres of the first column / row cancel (sigma * 1.2 - 0.1 near 0) and the bound, relative to |ref|, goes to
-    zero with them: the kernels evaluate those two channels in fp64 and round once (csrc/yolo_head.hip, eval_centre64)."""
+    zero with them: the kernels evaluate those two channels in fp64 and round once (csrc/yolo_decode.hip, eval_centre64)."""
     C, A, Fh, Fw, B, ldl = case
     lg, anc, v = _rect_logits(case)
     ref = LC.decode_ref64_rect(lg, ldl, B, Fh, Fw, A, C, anc, 8.0, scale)

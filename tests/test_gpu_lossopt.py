@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""Focal loss, IoU-aware objectness and the objectness / class gains of csrc/yolo_head.hip through the C ABI (the *_opts
+"""Focal loss, IoU-aware objectness and the objectness / class gains of csrc/yolo_loss.hip through the C ABI (the *_opts
 entries) against the float64 restatement of tests/lossopt_cases.py, then through YOLOLayer + YOLOLoss.
 
 With the defaults the new entries must give the bits -- workspace bytes included -- of the entries they generalise.

@@ -120,6 +120,46 @@ def test_default_options_are_postprocess(dev, kind):
             assert torch.equal(x.view(torch.int32), y.view(torch.int32)) and np.array_equal(y.cpu().numpy(), r)
 
 
+@gpu
+def test_postprocess_reaches_its_entries_through_lib_once_each(dev, monkeypatch):
+    """postprocess() runs on the driver it shares with postprocess_nms() / postprocess_wbf() and still looks its count and
+    NMS entries up on lib() when called (bench.py brackets them there): each is called once on 'four', the smallest of
+    HC.POST_KINDS, and wrapping changes neither the result nor the in-place xyxy.  An empty batch: the count entry refuses
+    it (Y4Error); postprocess_nms() gives []."""
+    from yolov4_amd import lib, ops
+    from yolov4_amd.yolo.util.utils import postprocess, postprocess_nms
+    p, C, conf, thre, props = _post_case('four')
+    assert any(r is not None for r in props['ref'])
+    plain_in = _up(p, dev)
+    plain = postprocess(plain_in, C, conf, thre)
+    L = lib()
+    calls = {'y4_post_count_f32': 0, 'y4_post_nms_f32': 0}
+
+    def counted(name):
+        fn = getattr(L, name)
+
+        def wrapper(*a):
+            calls[name] += 1
+            return fn(*a)
+        return wrapper
+    for name in calls:
+        monkeypatch.setattr(L, name, counted(name))
+    wrapped_in = _up(p, dev)
+    wrapped = postprocess(wrapped_in, C, conf, thre)
+    assert calls == {'y4_post_count_f32': 1, 'y4_post_nms_f32': 1}, calls
+    assert torch.equal(wrapped_in.view(torch.int32), plain_in.view(torch.int32))
+    assert np.array_equal(wrapped_in[:, :, :4].cpu().numpy().view(np.int32), props['xyxy'].view(np.int32))
+    assert len(wrapped) == len(plain) == len(props['ref'])
+    for x, y in zip(wrapped, plain):
+        assert (x is None) == (y is None)
+        if x is not None:
+            assert x.shape == y.shape and torch.equal(x.view(torch.int32), y.view(torch.int32))
+    empty = torch.empty((0, 8, 8), device=dev)
+    with pytest.raises(ops.Y4Error):
+        postprocess(empty, 3)
+    assert postprocess_nms(empty, 3) == []
+
+
 # ------------------------------------------------------------------------------------------ sizes x modes, exact
 EXACT_MODES = {'diou': dict(metric='diou'), 'linear': dict(soft='linear'), 'linear-diou': dict(soft='linear', metric='diou'),
                'agnostic': dict(agnostic=True), 'agnostic-linear': dict(agnostic=True, soft='linear'),

@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""The test-time-augmentation kernels (csrc/tta.hip) and weighted box fusion (csrc/yolo_head.hip) against
+"""The test-time-augmentation kernels (csrc/tta.hip) and weighted box fusion (csrc/postprocess.hip) against
 tests/fusion_cases.py's float32 restatements, bit for bit: rows, order and every float.  tests/test_fusion_cases.py shows
 without a GPU what each input contains.
 

@@ -16,7 +16,8 @@ CSRC = os.path.join(ROOT, 'yolov4_amd', 'csrc')
 
 
 @pytest.mark.parametrize('src,flags', [('conv_f16x2.hip', ()), ('conv_planes.hip', ()), ('conv_tile.hip', ()), ('pointwise.hip', ()),
-                                        ('yolo_head.hip', ('-ffp-contract=off',))])
+                                        ('yolo_decode.hip', ('-ffp-contract=off',)), ('yolo_loss.hip', ('-ffp-contract=off',)),
+                                        ('postprocess.hip', ('-ffp-contract=off',))])
 def test_no_kernel_uses_scratch(src, flags):
     path = os.path.join(CSRC, src)
     if not os.path.isfile(path):

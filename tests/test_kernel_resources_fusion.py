@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """The test-time-augmentation kernels (csrc/tta.hip) keep a lane's pixels / elements in registers: no scratch memory, no
-spills, no AGPRs, no LDS, full occupancy; the weighted-box-fusion kernel of csrc/yolo_head.hip uses no scratch and holds its
+spills, no AGPRs, no LDS, full occupancy; the weighted-box-fusion kernel of csrc/postprocess.hip uses no scratch and holds its
 cluster state in 45 KB of LDS (scripts/kernel_resources.py compiles the files for gfx950 and reads the code objects'
 metadata; no GPU needed)."""
 import os
@@ -26,7 +26,7 @@ def test_tta_kernels_no_scratch_no_spills():
 
 def test_wbf_kernel_uses_no_scratch():
     from kernel_resources import kernel_resources
-    rows = kernel_resources(os.path.join(ROOT, 'yolov4_amd', 'csrc', 'yolo_head.hip'), ('-ffp-contract=off',))
+    rows = kernel_resources(os.path.join(ROOT, 'yolov4_amd', 'csrc', 'postprocess.hip'), ('-ffp-contract=off',))
     wbf = [r for r in rows if 'post_wbf_kernel<' in r['name']]
     assert sorted(r['name'].split('(')[0] for r in wbf) == ['void post_wbf_kernel<false>', 'void post_wbf_kernel<true>']
     for r in wbf:

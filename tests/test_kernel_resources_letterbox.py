@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """The batch letterbox kernel (csrc/preprocess.hip) keeps a lane's four pixels in registers: no scratch memory, no spilled
 VGPRs, 16 bytes of LDS (the image's two scales), full occupancy (scripts/kernel_resources.py compiles the file for gfx950 and reads the code object's metadata; no GPU
-needed).  The rectangular decode instances of csrc/yolo_head.hip take the registers and LDS of the square ones."""
+needed).  The rectangular decode instances of csrc/yolo_decode.hip take the registers and LDS of the square ones."""
 import os
 import sys
 
@@ -25,7 +25,7 @@ def test_preprocess_kernels_no_scratch_no_spills():
 
 def test_rect_decode_instances_cost_what_the_square_ones_do():
     from kernel_resources import kernel_resources
-    rows = kernel_resources(os.path.join(ROOT, 'yolov4_amd', 'csrc', 'yolo_head.hip'), ('-ffp-contract=off',))
+    rows = kernel_resources(os.path.join(ROOT, 'yolov4_amd', 'csrc', 'yolo_decode.hip'), ('-ffp-contract=off',))
     tiled = {r['name'].split('(')[0]: r for r in rows if 'yolo_decode_tiled_kernel<true' in r['name']}
     assert len(tiled) == 8, sorted(tiled)
     for tp in (16, 32):

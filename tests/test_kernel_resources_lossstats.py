@@ -1,5 +1,5 @@
 # -*- coding: utf-8 -*-
-"""The loss-statistics kernels (csrc/yolo_head.hip) hold their eleven partial sums in registers:
+"""The loss-statistics kernels (csrc/yolo_loss.hip) hold their eleven partial sums in registers:
 no scratch memory, no spilled VGPRs, 352 B of LDS for the block reduction and 22 KB for the one-block fold
 (scripts/kernel_resources.py compiles the file for gfx950 and reads the code object's metadata; no GPU needed)."""
 import os
@@ -14,7 +14,7 @@ KERNELS = {'yolo_loss_stats_kernel': (33, 352), 'yolo_loss_stats_fold_kernel': (
 
 def test_no_scratch_no_spills_and_the_stated_registers_and_lds():
     from kernel_resources import kernel_resources
-    rows = kernel_resources(os.path.join(ROOT, 'yolov4_amd', 'csrc', 'yolo_head.hip'), ('-ffp-contract=off',))
+    rows = kernel_resources(os.path.join(ROOT, 'yolov4_amd', 'csrc', 'yolo_loss.hip'), ('-ffp-contract=off',))
     rows = [r for r in rows if r['name'].split('(')[0] in KERNELS]
     assert sorted(r['name'].split('(')[0] for r in rows) == sorted(KERNELS)
     for r in rows:

@@ -1,6 +1,6 @@
 // Anchor fitting on label shapes (Darknet's `detector calc_anchors`, the evolution stage of YOLOv5's autoanchor) as two
 // kernels: the assignment pass of one Lloyd iteration, and the fitness of many candidate anchor sets in one launch.
-// The shape IoU is the loss's (yolo_head.hip, yolo_assign_kernel): fp32, unfused (this file is built with
+// The shape IoU is the loss's (yolo_loss.hip, yolo_assign_kernel): fp32, unfused (this file is built with
 // -ffp-contract=off), IEEE division, first maximum wins.  Every sum is a sum of int64 fixed-point values (w, h: 2^-16;
 // IoU: 2^-30), so the results do not depend on block shape or arrival order.  Semantics: include/yolov4_amd.h, DESIGN.md §20.
 #include "common.h"

@@ -1,6 +1,6 @@
 # -*- coding: utf-8 -*-
 """Anchor fitting on a dataset's label shapes: what Darknet's `detector calc_anchors` and the evolution stage of YOLOv5's
-autoanchor do, with the metric the loss itself assigns by (the shape IoU of csrc/yolo_head.hip's yolo_assign_kernel).
+autoanchor do, with the metric the loss itself assigns by (the shape IoU of csrc/yolo_loss.hip's yolo_assign_kernel).
 
     label_shapes     (w, h) of every label, stretched to S x S, from an annotation file (no JPEG is decoded)
     kmeans_anchors   Lloyd iterations under the shape IoU, mean update

@@ -53,60 +53,12 @@ def postprocess(prediction, num_classes, conf_thre=0.7, nms_thre=0.45):
     """prediction [B,N,5+C] (xc,yc,w,h,obj,cls...) -> list of [n,7] tensors
     (x1,y1,x2,y2,obj,cls_conf,cls_id) or None; rows ordered class asc, score desc.
     Side effect kept from the reference: prediction[:, :, :4] becomes xyxy in place."""
-    L = lib()
-    src = prediction
-    on_host = not prediction.is_cuda
-    if on_host:                       # detect.py:115-118 moves the output to the CPU first
-        prediction = prediction.to(_dev())
-    if prediction.dtype != torch.float32 or not prediction.is_contiguous():
-        raise ops.Y4Error('postprocess expects a contiguous float32 [B,N,5+C] tensor')
-    B, N, n_ch = prediction.shape
-    if n_ch != 5 + num_classes:
-        raise ops.Y4Error('postprocess: last dim must be 5 + num_classes')
-    dev = prediction.device
-    out = [None for _ in range(B)]
-    if N == 0:
-        return out
-    nseg = B * num_classes
-    counts = torch.empty(nseg, dtype=torch.int32, device=dev)
-    st = ops._stream()
-    check(L.y4_post_count_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), 1, ops._ptr(counts), st),
-          'post_count')
-    if on_host:
-        src[:, :, :4] = prediction[:, :, :4].cpu()
-    # Everything between the count and the result stays on the device: prefix sums, key fill, sort + NMS, compaction run
-    # into buffers sized for `cap` candidates; the ONE host read at the end brings the per-image offsets and the true
-    # candidate total (if it exceeded cap -- many classes per box above a low threshold -- the sequence repeats with room).
-    cap = int(min(B * N * num_classes, max(B * N // 2, 1 << 16), (1 << 31) - 1))
-    seg_off = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
-    meta = torch.empty(2 + B + 1, dtype=torch.int32, device=dev)          # [total, overflow | img_off[0..B]]
-    out_off = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
-    kept = torch.empty(nseg, dtype=torch.int32, device=dev)
-    while True:
-        check(L.y4_post_scan_i32(ops._ptr(counts), nseg, cap, ops._ptr(seg_off), ops._ptr(meta), st), 'post_scan')
-        rows = torch.empty((cap, 7), dtype=torch.float32, device=dev)
-        final = torch.empty((cap, 7), dtype=torch.float32, device=dev)
+    def stage(L, pred, B, N, seg_off, cap, rows, kept, nseg, st):
         nbytes = L.y4_post_nms_workspace(cap, nseg)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(L.y4_post_nms_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), float(nms_thre),
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+        check(L.y4_post_nms_f32(ops._ptr(pred), B, N, num_classes, float(conf_thre), float(nms_thre),
                                 ops._ptr(seg_off), cap, ops._ptr(rows), ops._ptr(kept), ops._ptr(ws), nbytes, st), 'post_nms')
-        check(L.y4_post_compact_f32(ops._ptr(rows), ops._ptr(seg_off), ops._ptr(kept), B, num_classes, ops._ptr(final),
-                                    ops._ptr(out_off), ops._ptr(meta[2:]), st), 'post_compact')
-        host = meta.cpu().numpy().astype(np.int64)                        # the host sync
-        if not host[1]:
-            break
-        cap = int(host[0])
-    img_off = host[2:]
-    n_det = int(img_off[B])
-    if n_det == 0:
-        return out
-    dets = final[:n_det].clone()                                          # (lets the cap-sized buffers go)
-    if on_host:
-        dets = dets.cpu()
-    for b in range(B):
-        if img_off[b + 1] > img_off[b]:
-            out[b] = dets[img_off[b]:img_off[b + 1]]
-    return out
+    return _postprocess_segments('postprocess', prediction, num_classes, conf_thre, None, 0, stage)
 
 
 @dataclasses.dataclass
@@ -144,9 +96,11 @@ class NMSOptions:
 
 
 def _postprocess_segments(what, prediction, num_classes, conf_thre, agnostic, max_det, stage):
-    """The stages postprocess_nms() and postprocess_wbf() share: candidate count, then -- with the capacity retry and the one
-    host read -- scan, `stage(L, prediction, B, N, seg_off, cap, rows, kept, nseg, stream)` (key fill, sort and suppression or
-    fusion into rows / kept) and compaction or the per-image top-k.  Return contract and in-place xyxy side effect of postprocess()."""
+    """The driver of postprocess(), postprocess_nms() and postprocess_wbf(): candidate count, then -- with the capacity retry
+    and the one host read -- scan, `stage(L, prediction, B, N, seg_off, cap, rows, kept, nseg, stream)` (key fill, sort and
+    suppression or fusion into rows / kept) and compaction or the per-image top-k.  agnostic None is postprocess() itself: the
+    reference's rule through the plain count entry, which refuses an empty batch (the other two give [] for one).
+    detect.py:115-118 moves the output to the CPU first: a host tensor is taken to the device and gets its xyxy back."""
     L = lib()
     src = prediction
     on_host = not prediction.is_cuda
@@ -159,18 +113,23 @@ def _postprocess_segments(what, prediction, num_classes, conf_thre, agnostic, ma
         raise ops.Y4Error(what + ': last dim must be 5 + num_classes')
     dev = prediction.device
     out = [None for _ in range(B)]
-    if N == 0 or B == 0:
+    if N == 0 or (B == 0 and agnostic is not None):
         return out
-    agnostic = int(bool(agnostic))
     per_img = 1 if agnostic else num_classes
     nseg = B * per_img
     counts = torch.empty(nseg, dtype=torch.int32, device=dev)
     st = ops._stream()
-    check(L.y4_post_count_ex_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), 1, agnostic,
-                                 ops._ptr(counts), st), 'post_count_ex')
+    if agnostic is None:
+        check(L.y4_post_count_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), 1, ops._ptr(counts), st),
+              'post_count')
+    else:
+        check(L.y4_post_count_ex_f32(ops._ptr(prediction), B, N, num_classes, float(conf_thre), 1, int(bool(agnostic)),
+                                     ops._ptr(counts), st), 'post_count_ex')
     if on_host:
         src[:, :, :4] = prediction[:, :, :4].cpu()
-    # as in postprocess(): everything stays on the device until the one host read of the per-image offsets
+    # Everything between the count and the result stays on the device: prefix sums, key fill, sort + NMS, compaction run
+    # into buffers sized for `cap` candidates; the ONE host read at the end brings the per-image offsets and the true
+    # candidate total (if it exceeded cap -- many classes per box above a low threshold -- the sequence repeats with room).
     cap = int(min(B * N * num_classes, max(B * N // 2, 1 << 16), (1 << 31) - 1))
     seg_off = torch.empty(nseg + 1, dtype=torch.int32, device=dev)
     meta = torch.empty(2 + B + 1, dtype=torch.int32, device=dev)          # [total, overflow | img_off[0..B]]
@@ -198,7 +157,7 @@ def _postprocess_segments(what, prediction, num_classes, conf_thre, agnostic, ma
     n_det = int(img_off[B])
     if n_det == 0:
         return out
-    dets = final[:n_det].clone()
+    dets = final[:n_det].clone()                                          # (lets the cap-sized buffers go)
     if on_host:
         dets = dets.cpu()
     for b in range(B):
