@@ -84,6 +84,152 @@ def test_null_and_shape_errors_are_reported_before_any_launch():
     assert L.y4_conv2d_fwd_f32(fake, 32, fake, fake, 32, 1, 8, 8, 32, 32, 5, 1, None, None, 0, None, 0, None, None, fake, 1 << 30, None) == 1
 
 
+# the status codes as include/yolov4_amd.h defines them: Y4_OK 0, Y4_ERR_SHAPE 1, Y4_ERR_NULL 2, Y4_ERR_WORKSPACE 4
+# (_lib.py names only the JPEG codes ERR_FORMAT / ERR_UNSUPPORTED)
+OK, SHAPE, NULL, WORKSPACE = 0, 1, 2, 4
+ALL_MODES = (0, 1, 2, 3)
+
+
+def _conv_entry_early_returns(L):
+    """(entry, conv modes, arguments, expected status): calls of the conv entries (csrc/conv_api.hip, conv_stem.hip) that must
+    return before anything is launched, behind fake device pointers.  Defaults are a valid call; each case names what it changes."""
+    F, MIS = 0x1000, 0x1004
+    conv = dict(B=2, H=8, W=8, Cin=64, Cout=64, k=3, s=1)
+
+    def args(order, base, kw):
+        d = dict(base, **kw)
+        assert set(kw) <= set(base), kw
+        return [d[n] for n in order.split()]
+
+    fwd_o = 'x ldx w y ldy B H W Cin Cout k s scale shift act res ldr x_amax y_amax ws ws_bytes stream'
+    fwd_b = dict(conv, x=F, ldx=64, w=F, y=F, ldy=64, scale=None, shift=None, act=0, res=None, ldr=0, x_amax=None, y_amax=None,
+                 ws=F, ws_bytes=1 << 30, stream=None)
+    bn_o = 'x ldx w y ldy B H W Cin Cout k s partials partial_bytes nparts x_amax ws ws_bytes dgf dgf_bytes stream'
+    bn_b = dict(conv, x=F, ldx=64, w=F, y=F, ldy=64, partials=F, partial_bytes=1 << 30, nparts=F, x_amax=None, ws=F,
+                ws_bytes=1 << 30, dgf=None, dgf_bytes=0, stream=None)
+    pf_o = 'x ldx wp y ldy B H W Cin Cout k s scale shift act res ldr x_amax y_amax stream'
+    pf_b = dict(conv, x=F, ldx=64, wp=F, y=F, ldy=64, scale=None, shift=None, act=0, res=None, ldr=0, x_amax=None, y_amax=None,
+                stream=None)
+    pr_o = 'w Cout K prepared nbytes stream'
+    pr_b = dict(w=F, Cout=64, K=576, prepared=F, nbytes=1 << 30, stream=None)
+    dg_o = 'dy lddy w dx lddx B H W Cin Cout k s ws ws_bytes dy_amax res ldr stream'
+    dg_b = dict(conv, dy=F, lddy=64, w=F, dx=F, lddx=64, ws=F, ws_bytes=1 << 30, dy_amax=None, res=None, ldr=0, stream=None)
+    wg_o = 'x ldx dy lddy dw B H W Cin Cout k s ws ws_bytes x_amax dy_amax stream'
+    wg_b = dict(conv, B=4, H=38, W=38, x=F, ldx=64, dy=F, lddy=64, dw=F, ws=F, ws_bytes=1 << 30, x_amax=None, dy_amax=None,
+                stream=None)                                  # a split-K shape: the slabs go through the workspace in every mode
+    sf_o = 'x sxb sxc sxh sxw w y ldy B H W Cout scale shift act stats stream'
+    sf_b = dict(x=F, sxb=3 * 64 * 64, sxc=64 * 64, sxh=64, sxw=1, w=F, y=F, ldy=32, B=2, H=64, W=64, Cout=32, scale=None,
+                shift=None, act=0, stats=None, stream=None)
+    sw_o = 'x sxb sxc sxh sxw dy lddy dw B H W Cout ws ws_bytes stream'
+    sw_b = dict(x=F, sxb=3 * 64 * 64, sxc=64 * 64, sxh=64, sxw=1, dy=F, lddy=32, dw=F, B=2, H=64, W=64, Cout=32, ws=F,
+                ws_bytes=1 << 30, stream=None)
+    am_o = 'x ldx M C out stream'
+    am_b = dict(x=F, ldx=64, M=100, C=64, out=F, stream=None)
+    mg_o = 'dst src stream'
+    mg_b = dict(dst=F, src=F, stream=None)
+
+    fwd_ws = L.y4_conv2d_fwd_workspace(64, 64, 3)
+    dg_ws = L.y4_conv2d_dgrad_workspace(64, 64, 3)
+    bn_ws = L.y4_conv2d_bnstats_workspace(2, 8, 8, 64, 64, 3, 1)
+    pr_ws = L.y4_conv2d_prepared_bytes(64, 576)
+    wg_ws = L.y4_conv2d_wgrad_workspace(4, 38, 38, 64, 64, 3, 1)
+    sw_ws = L.y4_conv2d_stem_wgrad_workspace(2, 64, 64, 32)
+    assert wg_ws > 64 and bn_ws > 0
+
+    split = (1, 2, 3)                                           # the modes whose forward takes a workspace
+    cases = []
+
+    def add(entry, order, base, rows):
+        for modes, kw, want in rows:
+            cases.append((entry, modes, args(order, base, kw), want, kw))
+
+    add('y4_conv2d_fwd_f32', fwd_o, fwd_b, [
+        (ALL_MODES, dict(x=None, k=5), NULL), (ALL_MODES, dict(w=None, B=0), NULL),
+        (ALL_MODES, dict(y=None, Cin=48), NULL),
+        (ALL_MODES, dict(k=5, ws_bytes=0), SHAPE), (ALL_MODES, dict(s=3, ws_bytes=0), SHAPE), (ALL_MODES, dict(Cin=48, ldx=48), SHAPE),
+        (ALL_MODES, dict(Cin=32, ldx=31), SHAPE), (ALL_MODES, dict(ldy=63), SHAPE), (ALL_MODES, dict(ldx=66), SHAPE),
+        (ALL_MODES, dict(x=MIS), SHAPE), (ALL_MODES, dict(res=F, ldr=63, ws_bytes=0), SHAPE),
+        (ALL_MODES, dict(B=128, H=4096, W=4096, Cin=32, ldx=32, k=1, ws_bytes=0), SHAPE),        # M = 2^31
+        (split, dict(ws=None), NULL), (split, dict(ws=None, ws_bytes=0), NULL),
+        (split, dict(ws_bytes=fwd_ws - 1), WORKSPACE), (split, dict(ws=MIS, ws_bytes=fwd_ws - 1), WORKSPACE),
+        (split, dict(ws=MIS), SHAPE)])
+    add('y4_conv2d_fwd_bnstats_f32', bn_o, bn_b, [
+        (ALL_MODES, dict(partials=None, k=5), NULL), (ALL_MODES, dict(nparts=None, partial_bytes=0), NULL),
+        (ALL_MODES, dict(x=None, k=5), NULL),
+        ((0, 1, 2), dict(dgf=F, dgf_bytes=1 << 30), SHAPE),            # a dgrad_filter outside mode 3
+        ((0, 1, 2), dict(dgf=F, dgf_bytes=1 << 30, partial_bytes=0), SHAPE), ((0, 1, 2), dict(dgf=F, x=None), SHAPE),
+        (ALL_MODES, dict(partial_bytes=bn_ws - 1), WORKSPACE),
+        (ALL_MODES, dict(partial_bytes=bn_ws - 1, x=None), WORKSPACE),    # the partial rows are checked before the conv's operands
+        (ALL_MODES, dict(k=5, partial_bytes=0, ws_bytes=0), SHAPE), (ALL_MODES, dict(Cin=48, ldx=48, partial_bytes=1 << 30), SHAPE),
+        (split, dict(ws_bytes=fwd_ws - 1, partial_bytes=bn_ws), WORKSPACE), (split, dict(ws=None), NULL),
+        ((3,), dict(dgf=F, dgf_bytes=dg_ws - 1), WORKSPACE), ((3,), dict(dgf=MIS, dgf_bytes=dg_ws - 1), WORKSPACE),
+        ((3,), dict(dgf=MIS, dgf_bytes=dg_ws), SHAPE), ((3,), dict(dgf=F, dgf_bytes=dg_ws, ws_bytes=fwd_ws - 1), WORKSPACE)])
+    add('y4_conv2d_fwd_prepared_f32', pf_o, pf_b, [
+        (ALL_MODES, dict(wp=None, k=5), NULL), (ALL_MODES, dict(x=None, k=5), NULL), (ALL_MODES, dict(y=None, Cin=33), NULL),
+        (ALL_MODES, dict(k=5), SHAPE), (ALL_MODES, dict(Cin=33, ldx=36), SHAPE), (ALL_MODES, dict(ldy=63), SHAPE),
+        ((0, 1, 2), dict(), SHAPE),                                     # prepared filters are f16x2 planes: mode 3 only
+        ((3,), dict(wp=MIS), SHAPE)])
+    add('y4_conv2d_prepare_filter_f32', pr_o, pr_b, [
+        (ALL_MODES, dict(w=None, K=31), NULL), (ALL_MODES, dict(prepared=None, Cout=0), NULL),
+        (ALL_MODES, dict(K=31, nbytes=0), SHAPE), (ALL_MODES, dict(Cout=0, nbytes=0), SHAPE),
+        (ALL_MODES, dict(nbytes=pr_ws - 1), WORKSPACE), (ALL_MODES, dict(prepared=MIS, nbytes=pr_ws - 1), WORKSPACE),
+        (ALL_MODES, dict(prepared=MIS, nbytes=pr_ws), SHAPE), (ALL_MODES, dict(w=MIS), SHAPE)])
+    add('y4_conv2d_dgrad_f32', dg_o, dg_b, [
+        (ALL_MODES, dict(dy=None, k=5), NULL), (ALL_MODES, dict(dx=None, Cin=0), NULL), (ALL_MODES, dict(ws=None, k=5), NULL),
+        ((0, 1, 2), dict(w=None), NULL), ((0, 1, 2), dict(w=None, k=5), NULL),
+        ((3,), dict(w=None, k=5), SHAPE), ((3,), dict(w=None, ws_bytes=dg_ws - 1), WORKSPACE),    # w == NULL passes in mode 3
+        (ALL_MODES, dict(k=5, ws_bytes=0), SHAPE), (ALL_MODES, dict(Cin=0, ws_bytes=0), SHAPE), (ALL_MODES, dict(lddy=63, ws_bytes=0), SHAPE),
+        (ALL_MODES, dict(Cout=33, lddy=36), SHAPE), (ALL_MODES, dict(lddx=63), SHAPE), (ALL_MODES, dict(lddy=66), SHAPE),
+        (ALL_MODES, dict(ws_bytes=dg_ws - 1), WORKSPACE), (ALL_MODES, dict(ws=MIS, ws_bytes=dg_ws - 1), WORKSPACE),
+        (ALL_MODES, dict(ws=MIS, ws_bytes=dg_ws), SHAPE), (ALL_MODES, dict(dy=MIS), SHAPE)])
+    add('y4_conv2d_wgrad_f32', wg_o, wg_b, [
+        (ALL_MODES, dict(x=None, k=5), NULL), (ALL_MODES, dict(dy=None, Cin=0), NULL), (ALL_MODES, dict(dw=None, ws_bytes=0), NULL),
+        (ALL_MODES, dict(k=5, ws_bytes=0), SHAPE), (ALL_MODES, dict(s=0, ws_bytes=0), SHAPE), (ALL_MODES, dict(Cin=30, ldx=32, ws_bytes=0), SHAPE),
+        (ALL_MODES, dict(ldx=63), SHAPE), (ALL_MODES, dict(lddy=62), SHAPE), (ALL_MODES, dict(lddy=60), SHAPE), (ALL_MODES, dict(x=MIS), SHAPE),
+        (ALL_MODES, dict(ws=None), NULL), (ALL_MODES, dict(ws_bytes=wg_ws - 65), WORKSPACE), (ALL_MODES, dict(ws_bytes=0), WORKSPACE),
+        ((3,), dict(ws_bytes=wg_ws - 1), WORKSPACE), ((3,), dict(ws_bytes=wg_ws - 1, x_amax=F), WORKSPACE)])   # the amax words
+    add('y4_conv2d_stem_fwd_f32', sf_o, sf_b, [
+        (ALL_MODES, dict(x=None, Cout=33), NULL), (ALL_MODES, dict(w=None, B=0), NULL), (ALL_MODES, dict(y=None), NULL),
+        (ALL_MODES, dict(Cout=33, ldy=33), SHAPE), (ALL_MODES, dict(Cout=0), SHAPE), (ALL_MODES, dict(ldy=31), SHAPE),
+        (ALL_MODES, dict(B=0), SHAPE), (ALL_MODES, dict(W=-1), SHAPE),
+        (ALL_MODES, dict(B=1, H=1 << 20, W=1 << 20), SHAPE)])           # 2^32 blocks
+    add('y4_conv2d_stem_wgrad_f32', sw_o, sw_b, [
+        (ALL_MODES, dict(ws=None, W=1), NULL), (ALL_MODES, dict(x=None, Cout=33), NULL), (ALL_MODES, dict(dw=None, ws_bytes=0), NULL),
+        (ALL_MODES, dict(W=1, ws_bytes=0), SHAPE), (ALL_MODES, dict(Cout=33, ws_bytes=0), SHAPE), (ALL_MODES, dict(lddy=31, ws_bytes=0), SHAPE),
+        (ALL_MODES, dict(ws_bytes=sw_ws - 1), WORKSPACE), (ALL_MODES, dict(ws_bytes=sw_ws - 1, sxw=-1), WORKSPACE),
+        (ALL_MODES, dict(ws_bytes=sw_ws, sxw=-1), SHAPE), (ALL_MODES, dict(ws_bytes=sw_ws, sxb=1 << 30), SHAPE),     # 32-bit window
+        (ALL_MODES, dict(ws_bytes=sw_ws, B=128, H=608, W=608, lddy=1 << 26), SHAPE)])                                   # a wave's dy rows
+    add('y4_amax_f32', am_o, am_b, [
+        (ALL_MODES, dict(x=None, C=0), NULL), (ALL_MODES, dict(out=None, M=-1), NULL),
+        (ALL_MODES, dict(C=0), SHAPE), (ALL_MODES, dict(M=-1), SHAPE), (ALL_MODES, dict(ldx=63), SHAPE)])
+    add('y4_amax_merge_u32', mg_o, mg_b, [(ALL_MODES, dict(dst=None), NULL), (ALL_MODES, dict(src=None), NULL),
+                                         (ALL_MODES, dict(dst=None, src=None), NULL)])
+    return cases
+
+
+def test_conv_entries_report_null_then_shape_then_workspace_before_any_launch():
+    """Every conv entry checks NULL operands, then shapes and pitches, then workspace sizes, in that order and before it
+    launches anything; in which modes a case applies is part of the table (w == NULL for dgrad is allowed in mode 3 only, a
+    dgrad_filter for the BN-statistics forward in mode 3 only, the forward takes a workspace in modes 1-3)."""
+    L = yolov4_amd.lib()
+    cases = _conv_entry_early_returns(L)
+    assert {c[0] for c in cases} == {
+        'y4_conv2d_fwd_f32', 'y4_conv2d_fwd_bnstats_f32', 'y4_conv2d_fwd_prepared_f32', 'y4_conv2d_prepare_filter_f32',
+        'y4_conv2d_dgrad_f32', 'y4_conv2d_wgrad_f32', 'y4_conv2d_stem_fwd_f32', 'y4_conv2d_stem_wgrad_f32', 'y4_amax_f32',
+        'y4_amax_merge_u32'}
+    was = L.y4_get_conv_mode()
+    try:
+        assert L.y4_set_conv_mode(-1) == SHAPE and L.y4_set_conv_mode(4) == SHAPE and L.y4_get_conv_mode() == was
+        for mode in ALL_MODES:
+            assert L.y4_set_conv_mode(mode) == OK and L.y4_get_conv_mode() == mode
+            for entry, modes, a, want, what in cases:
+                if mode in modes:
+                    got = getattr(L, entry)(*a)
+                    assert got == want, (entry, mode, what, got, want)
+    finally:
+        L.y4_set_conv_mode(was)
+
+
 def test_state_dict_matches_reference_tree():
     m = YOLOv4(recipe.MODEL_CFG)
     sd = m.state_dict()

@@ -202,6 +202,38 @@ def test_conv1x1_streaming_kernel(dev, B, ci, co, H):
     assert int(nbt) == 1
 
 
+@pytest.mark.parametrize('H,ci,co', [(257, 32, 32), (257, 64, 96), (257, 128, 128), (257, 128, 64), (255, 64, 64)])
+def test_conv1x1_streaming_kernel_bf16x3(dev, H, ci, co):
+    """conv1x1_stream_bf16x3 (conv mode 1; conv_igemm.hip picks it for 1x1 stride 1, K in {32, 64, 128}, N <= 128 and
+    M >= 131072) through the forward, the BN-statistics forward and dgrad, against fp64.  B = 2, H = W = 257: M = 132098, the
+    smallest square map above the threshold and no multiple of the 128-row tile.  (32, 32): the smallest channel counts;
+    (64, 96): a partly masked column tile, and dgrad (Cs = 96) takes the gather kernel; (128, 128): the 8-wave variant with
+    one block per CU.  H = 255: M = 130050 lies below the threshold and the same calls take the gather kernel."""
+    import yolov4_amd
+    from yolov4_amd import ops
+    B = 2
+    g = torch.Generator().manual_seed(B * 1000 + ci + co + H)
+    x = cl(torch.randn((B, ci, H, H), generator=g), dev)
+    w = cl(torch.randn((co, ci, 1, 1), generator=g) * 0.1, dev)
+    dy = cl(torch.randn((B, co, H, H), generator=g), dev)
+    ref = F.conv2d(x.double(), w.double())
+    dref = F.conv_transpose2d(dy.double(), w.double())
+    old = yolov4_amd.get_conv_mode()
+    yolov4_amd.set_conv_mode('bf16x3')
+    try:
+        tight(ops.conv_fwd_raw(x, w, 1, 1), ref.cpu(), rel=1e-5)
+        tight(ops.conv_dgrad_raw(dy, w, (B, ci, H, H), 1, 1), dref.cpu(), rel=1e-5)
+        rm, rv = torch.zeros(co, device=dev), torch.ones(co, device=dev)
+        nbt = torch.zeros((), dtype=torch.long, device=dev)
+        y, mean, invstd = ops.conv_fwd_bnstats_raw(x, w, 1, 1, rm, rv, nbt, 0.1, 1e-5)
+        tight(y, ref.cpu(), rel=1e-5)
+        close(mean, ref.mean(dim=(0, 2, 3)), 1e-6, 1e-5, scale=False)
+        close(invstd, (ref.var(dim=(0, 2, 3), unbiased=False) + 1e-5).rsqrt(), 1e-6, 1e-5, scale=False)
+        assert int(nbt) == 1
+    finally:
+        yolov4_amd.set_conv_mode(old)
+
+
 def test_conv_non_finite_inputs_stay_non_finite(dev, conv_mode):
     """A NaN or Inf activation must not be laundered into a finite number by the operand split (bf16x3: x - trunc(x)
     of an Inf is NaN, so an Inf input surfaces as NaN where the fp32 chain gives +-Inf -- both are non-finite)."""

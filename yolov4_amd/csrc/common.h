@@ -119,7 +119,7 @@ __device__ __forceinline__ f32x4 y4_buf_load4(__amdgpu_buffer_rsrc_t r, unsigned
     return __builtin_bit_cast(f32x4, v);
 }
 
-// ---- the bf16x3 split (conv_igemm.hip, stem_fused.hip): an fp32 value as the exact sum of three truncated bf16 pieces
+// ---- the bf16x3 split (conv_igemm.hip, conv_stem.hip, stem_fused.hip): an fp32 value as the exact sum of three truncated bf16 pieces
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 // pack the upper halves (= truncated bf16) of two fp32 words: result = {hi16(x1), hi16(x0)}
@@ -181,6 +181,6 @@ int bn_bwd_fold_finalize(const float* part, long long nparts, long long M, int C
 int bn_bwd_reduce_finalize_bounds(const float* dz, int lddz, const float* y, int ldy, const float* mean, const float* invstd,
                                   const float* gamma, const float* beta, int act, long long M, int C, void* workspace,
                                   float* dgamma, float* dbeta, unsigned* bounds, hipStream_t st);
-// conv_igemm.hip: per-wave slabs [nslabs][32 n][32 j] -> dw[Cout][27] through part[64][1024] doubles, fixed order
+// conv_stem.hip: per-wave slabs [nslabs][32 n][32 j] -> dw[Cout][27] through part[64][1024] doubles, fixed order
 int stem_wgrad_fold(const float* slabs, int nslabs, double* part, float* dw, int Cout, hipStream_t st);
 }  // namespace y4

@@ -1,5 +1,5 @@
 // Problem descriptors shared by the implicit-GEMM convolution kernels (conv_igemm.hip: fp32-MFMA, bf16x3, bf16;
-// conv_f16x2.hip: the two-piece fp16 split).
+// conv_f16x2.hip: the two-piece fp16 split) and the host routines the conv entries (conv_api.hip) route to.
 #pragma once
 #include "common.h"
 
@@ -60,12 +60,17 @@ int f16x2_filter_planes_dual(const float* w, unsigned short* planes, unsigned* a
                              unsigned* amax_out_t, int Cout, int Cin, int kk, int Cout_pad, bool mirror, hipStream_t st);
 int f16x2_filter_planes_transposed(const float* w, unsigned short* planes, int Cout, int Cin, int kk, int Cout_pad,
                                    unsigned* amax_out, unsigned* part, hipStream_t st, bool mirror = false);
-// conv_igemm.hip: dw[n] = sum over `splits` fp32 slabs of n elements each, fixed order (deterministic)
+// conv_igemm.hip: conv modes 0 (fp32 MFMA), 1 (bf16x3) and 2 (bf16), the mode handed in by the caller.
+// igemm_filter: the filter as the gather kernels of `mode` read it, into `out` -- forward: bf16 planes [Cout][kk Cin] (modes 1
+// and 2 only: mode 0 reads the fp32 filter as it lies); transposed, for dgrad: [Cin][kk][Cout padded to 32] as fp32 (mode 0) or as bf16 planes
+int igemm_filter(int mode, const float* w, void* out, int Cout, int Cin, int kk, bool transposed, hipStream_t st);
+int igemm_gather(int mode, const ConvGeom& g, bool transposed, hipStream_t st, int* nparts);
+int igemm_wgrad(int mode, const WgradGeom& g, hipStream_t st);     // tile g.tn x g.tj, g.splits slabs
+// conv_api.hip: dw[n] = sum over `splits` fp32 slabs of n elements each, fixed order (deterministic)
 int slab_reduce(const float* slabs, float* dw, long long n, int splits, hipStream_t st);
 int amax_launch(const float* x, long long ld, long long M, int C, unsigned* amax_bits, hipStream_t st,
                 bool prezeroed = false);     // zeroes the word first unless the caller hands in a zeroed one
 int amax_merge(unsigned* dst, const unsigned* src, hipStream_t st);
-
 
 // conv_tile.hip: 3x3 stride-1 layers with few channels on large maps (2-D tiles, every input element staged once);
 // forward form only: dgrad hands in the mirrored transposed filter planes
@@ -95,7 +100,7 @@ int planes_wgrad(const void* x, const unsigned* x_amax, const void* dy, const un
                  size_t workspace_bytes, int B, int H, int W, int Cin, int Cout, int k, hipStream_t st, bool bf = false,
                  int stride = 1);
 
-// Name of the conv kernel launched last on this host thread, spelled as rocprofv3 prints the symbol (bench.py names the
+// conv_api.hip: name of the conv kernel launched last on this host thread, spelled as rocprofv3 prints the symbol (bench.py names the
 // dominant kernel with it instead of restating the dispatch rules).
 void note_kernel(const char* fmt, ...);
 }  // namespace y4

@@ -10,16 +10,10 @@
 // Tile: 256 threads = 4 waves; each wave owns TM x TN tiles of 32x32 (16 accumulator VGPRs each).
 // LDS: [rows][BK + 4] floats (row pitch 144 B -> ds_read_b128 conflict-free across the 16-lane
 // groups), double buffered, register-staged global loads issued one K-tile ahead.
-#include <stdlib.h>
 #include "common.h"
-#include <cstdarg>
-#include <cstdio>
 #include "conv_geom.h"
 
 namespace {
-
-constexpr int BK = 32;            // K-tile depth (floats)
-
 
 using y4::ConvGeom;
 using y4::WgradGeom;
@@ -627,17 +621,6 @@ __global__ void transpose_split_filter_kernel(const float* __restrict__ w, unsig
     }
 }
 
-thread_local char g_last_kernel[160] = "";          // see y4::note_kernel
-}
-namespace y4 {
-void note_kernel(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_last_kernel, sizeof(g_last_kernel), fmt, ap);
-    va_end(ap);
-}
-}
-namespace {
 template <int BM, int BN, int WM, int WN, bool TR, int BKT = 32, int NP = 0>
 int launch_gather(const ConvGeom& g0, hipStream_t st) {
     constexpr bool SPLIT = NP > 0;
@@ -692,10 +675,6 @@ int launch_gather(const ConvGeom& g0, hipStream_t st) {
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
-
-int g_conv_mode = 3;          // 0: fp32 MFMA (exact fma chain), 1: split-bf16 x3 (fp32-grade, 6 bf16 MFMAs),
-                              // 2: plain bf16 operands (RN), fp32 accumulate -- mixed precision, BASELINE config 5
-                              // 3: split-fp16 x2 (fp32-grade, 3 fp16 MFMAs, per-tensor power-of-two scale; conv_f16x2.hip) -- default
 
 // ---------------------------------------------------------------- streaming 1x1 kernel (small K, small N)
 // The 1x1 layers on the 304^2 / 152^2 maps are HBM-bound (K, N <= 128: < 64 flop per byte); the tile machinery
@@ -879,8 +858,8 @@ int launch_stream1x1(const ConvGeom& g0, hipStream_t st, int* nparts) {
 
 // eligibility: bf16x3 arithmetic, 1x1 stride 1, K in {32,64,128}, N <= 128, filter planes <= 52 KB of LDS,
 // 32-bit addressable source, every source channel valid, and enough rows to be worth a persistent launch
-static bool stream1x1_ok(const ConvGeom& g) {
-    if (g_conv_mode != 1 || g.k != 1 || g.stride != 1 || !g.wt_planes) return false;
+static bool stream1x1_ok(int mode, const ConvGeom& g) {
+    if (mode != 1 || g.k != 1 || g.stride != 1 || !g.wt_planes) return false;
     if (g.Cs != 32 && g.Cs != 64 && g.Cs != 128) return false;
     if (g.Cs_valid != g.Cs || g.N > 128) return false;
     const int n32 = (g.N + 31) / 32 * 32;
@@ -905,14 +884,19 @@ static int dispatch_stream1x1(const ConvGeom& g, hipStream_t st, int* nparts) {
     }
 }
 
+// the bf16 kernels on one tile: a single rounded plane (mode 2) or the three-piece split (mode 1)
+template <int BM, int BN, int WM, int WN, bool TR>
+int launch_gather_bf16(bool one, const ConvGeom& g, hipStream_t st) {
+    return one ? launch_gather<BM, BN, WM, WN, TR, 32, 1>(g, st) : launch_gather<BM, BN, WM, WN, TR, 32, 3>(g, st);
+}
 
 template <bool TR>
-int dispatch_gather(const ConvGeom& g, hipStream_t st, int* nparts = nullptr) {
+int dispatch_gather(int mode, const ConvGeom& g, hipStream_t st, int* nparts) {
     // *nparts: number of BN-statistics partial rows the launch writes (M tiles, or blocks of the streaming kernel)
     if (nparts) *nparts = (g.M + 127) / 128;
-    if (stream1x1_ok(g)) return dispatch_stream1x1(g, st, nparts);
-    if (g_conv_mode == 1 || g_conv_mode == 2) {
-        const bool one = g_conv_mode == 2;
+    if (stream1x1_ok(mode, g)) return dispatch_stream1x1(g, st, nparts);
+    if (mode == 1 || mode == 2) {
+        const bool one = mode == 2;
         if (g.N > 64) {
             const long long nt = (g.N + 127) / 128;
             const long long b128 = ((long long)g.M + 127) / 128 * nt, b64 = ((long long)g.M + 63) / 64 * nt;
@@ -920,12 +904,12 @@ int dispatch_gather(const ConvGeom& g, hipStream_t st, int* nparts = nullptr) {
             const double c64 = (double)((b64 + 511) / 512) * 64.0 * 1.10;
             if (c64 < c128 && !(TR && g.stride == 2)) {
                 if (nparts) *nparts = (g.M + 63) / 64;
-                return one ? launch_gather<64, 128, 2, 2, TR, 32, 1>(g, st) : launch_gather<64, 128, 2, 2, TR, 32, 3>(g, st);
+                return launch_gather_bf16<64, 128, 2, 2, TR>(one, g, st);
             }
-            return one ? launch_gather<128, 128, 2, 2, TR, 32, 1>(g, st) : launch_gather<128, 128, 2, 2, TR, 32, 3>(g, st);
+            return launch_gather_bf16<128, 128, 2, 2, TR>(one, g, st);
         }
-        if (g.N > 32) return one ? launch_gather<128, 64, 2, 2, TR, 32, 1>(g, st) : launch_gather<128, 64, 2, 2, TR, 32, 3>(g, st);
-        return one ? launch_gather<128, 32, 4, 1, TR, 32, 1>(g, st) : launch_gather<128, 32, 4, 1, TR, 32, 3>(g, st);
+        if (g.N > 32) return launch_gather_bf16<128, 64, 2, 2, TR>(one, g, st);
+        return launch_gather_bf16<128, 32, 4, 1, TR>(one, g, st);
     }
     if (g.N > 64) {
         // LDS allows 2 resident blocks per CU at BK = 32 (74 KB) and 3 at BK = 16 (41 KB).  1x1 convs have
@@ -1292,92 +1276,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16x3(const WgradGeom g) {
     }
 }
 
-// vector variant: a block owns VEC float4 columns; its 256/VEC thread groups each add every (256/VEC)-th slab
-// (4 independent loads in flight), then the groups are combined through LDS in group order -- a fixed
-// summation tree for a given split count, hence deterministic, and hundreds of slabs no longer serialise
-// behind one thread's load latency.
-template <int VEC>
-__global__ __launch_bounds__(256) void slab_reduce_vec_kernel(const f32x4* __restrict__ slabs, f32x4* __restrict__ out,
-                                                              long long nvec, int splits) {
-    constexpr int SG = 256 / VEC;
-    __shared__ f32x4 red[SG][VEC];
-    const int v = threadIdx.x % VEC, sg = threadIdx.x / VEC;
-    const long long i = (long long)blockIdx.x * VEC + v;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, s2 = s0, s3 = s0;
-    if (i < nvec) {
-        int k = sg;
-        for (; k + 3 * SG < splits; k += 4 * SG) {
-            const f32x4 a = slabs[(long long)k * nvec + i], b = slabs[(long long)(k + SG) * nvec + i];
-            const f32x4 c = slabs[(long long)(k + 2 * SG) * nvec + i], d = slabs[(long long)(k + 3 * SG) * nvec + i];
-            s0 += a; s1 += b; s2 += c; s3 += d;
-        }
-        for (; k < splits; k += SG) s0 += slabs[(long long)k * nvec + i];
-    }
-    red[sg][v] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (sg == 0 && i < nvec) {
-        f32x4 t = red[0][v];
-#pragma unroll
-        for (int g = 1; g < SG; ++g) t += red[g][v];
-        out[i] = t;
-    }
-}
-
-__global__ void slab_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ out,
-                                   long long n, int splits) {
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
-         i += (long long)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        for (int k = 0; k < splits; ++k) s += slabs[(long long)k * n + i];   // fixed order
-        out[i] = s;
-    }
-}
-
-void wgrad_plan(int B, int H, int W, int Cin, int Cout, int k, int stride, WgradGeom& g) {
-    const int pad = (k - 1) / 2;
-    g.B = B; g.H = H; g.W = W; g.Cin = Cin; g.Cout = Cout; g.k = k; g.stride = stride; g.pad = pad;
-    g.Ho = (H + 2 * pad - k) / stride + 1;
-    g.Wo = (W + 2 * pad - k) / stride + 1;
-    g.M = B * g.Ho * g.Wo;
-    g.J = k * k * Cin;
-    g.tn = Cout <= 64 ? 64 : 128;
-    g.tj = g.J <= 64 ? 64 : 128;
-    g.ntn = (Cout + g.tn - 1) / g.tn;
-    g.ntj = (g.J + g.tj - 1) / g.tj;
-    const int tiles = g.ntn * g.ntj;
-    const int chunks = (g.M + 31) / 32;
-    // resident blocks: LDS = 2*32*(tn+tj)*4 B per block, 160 KiB per CU, <= 8 (wave slots at 4 waves/block)
-    int per_cu = (160 * 1024) / (2 * 32 * (g.tn + g.tj) * 4);
-    if (per_cu > 4) per_cu = 4;
-    if (g.tn + g.tj == 256 && per_cu > 2) per_cu = 2;      // 128x128: 124 VGPRs + 64 KiB
-    const int slots = 256 * per_cu;
-    // choose the split count in [1, chunks/16] that fills whole rounds of `slots` blocks best
-    int max_s = chunks / 16;
-    if (max_s < 1) max_s = 1;
-    if (max_s > 4096) max_s = 4096;
-    int best_s = 1;
-    double best_eff = -1.0;
-    for (int sp = 1; sp <= max_s; ++sp) {
-        const long long blocks = (long long)tiles * sp;
-        const long long rounds = (blocks + slots - 1) / slots;
-        double eff = (double)blocks / (double)(rounds * slots);
-        if (rounds > 6) eff = 1.0;                           // enough rounds: tail is amortised
-        if (eff > best_eff + 0.02) { best_eff = eff; best_s = sp; }
-        if (blocks >= 2ll * slots && eff >= 0.93) break;     // good enough: fewer slabs to write and fold
-        if (blocks >= 6ll * slots) break;
-    }
-    { static const char* fs = getenv("Y4_WGRAD_SPLITS"); if (fs) { best_s = atoi(fs); if (best_s > max_s) best_s = max_s; if (best_s < 1) best_s = 1; } }
-    g.chunks_per_split = (chunks + best_s - 1) / best_s;
-    // a block's pixel range (+ 2 images of slack) must fit a 32-bit buffer window; planned for pitches up to 2x the
-    // channel count (channel slices of concat buffers), verified against the real pitches at call time
-    const unsigned long long per_px = 8ull * (unsigned long long)((Cout + 3) / 4 * 4 > Cin * stride * stride ? (Cout + 3) / 4 * 4 : Cin * stride * stride);
-    const unsigned long long slack = 2ull * g.Ho * g.Wo;
-    const unsigned long long max_px = 0xf0000000ull / per_px;
-    if (max_px > slack + 32 && (unsigned long long)g.chunks_per_split * 32ull + slack > max_px)
-        g.chunks_per_split = (int)((max_px - slack) / 32ull);
-    g.splits = (chunks + g.chunks_per_split - 1) / g.chunks_per_split;
-}
-
 template <int TN_, int TJ_, int NP = 0>
 int launch_wgrad(const WgradGeom& g, hipStream_t st) {
     constexpr bool SPLIT = NP > 0;
@@ -1392,726 +1290,40 @@ int launch_wgrad(const WgradGeom& g, hipStream_t st) {
     return Y4_OK;
 }
 
-// ------------------------------------------------------------------------------------ stem
-// Cin = 3, k = 3, stride 1, pad 1 (yolo/model/yolov4.py:30).  One thread per output pixel, all
-// Cout (<= 32) channels in registers, filter taps come in through the scalar path (uniform
-// addresses); the 128-B pixel rows are transposed through LDS so stores are lane-contiguous.
-struct StemGeom {
-    const float* x; const float* w; float* y; const float* scale; const float* shift;
-    float* stats;                 // optional [blocks][2][Cout] column sums of the (raw) output
-    long long sxb, sxc, sxh, sxw, ldy;
-    int B, H, W, Cout, act;
-    long long M;
-};
-
-__global__ __launch_bounds__(256) void conv_stem_fwd_kernel(const StemGeom g) {
-    __shared__ float tile[4][64][33];
-    __shared__ __attribute__((aligned(16))) float wl[27 * 32];          // filter, [tap*3+c][n] (n contiguous)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < 27 * 32; i += 256) {
-        const int n = i & 31, kk = i >> 5;
-        wl[i] = n < g.Cout ? g.w[n * 27 + kk] : 0.f;
-    }
-    __syncthreads();
-    const long long pix0 = (long long)blockIdx.x * 256 + wave * 64;
-    const long long pix = pix0 + lane;
-    float acc[32];
-#pragma unroll
-    for (int n = 0; n < 32; ++n) acc[n] = 0.f;
-    if (pix < g.M) {
-        const int b = (int)(pix / ((long long)g.H * g.W));
-        const int rem = (int)(pix - (long long)b * g.H * g.W);
-        const int h = rem / g.W, w = rem - h * g.W;
-        const float* xb = g.x + b * g.sxb;
-        float xv[27];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const int hi = h + r - 1, wi = w + q - 1;
-                const bool ok = (unsigned)hi < (unsigned)g.H && (unsigned)wi < (unsigned)g.W;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) xv[(r * 3 + q) * 3 + c] = ok ? xb[c * g.sxc + hi * g.sxh + wi * g.sxw] : 0.f;
-            }
-        // taps one at a time (sched_barrier keeps the 216 LDS broadcasts from being hoisted into 864 registers)
-#pragma unroll
-        for (int kk = 0; kk < 27; ++kk) {
-            const f32x4* wp = reinterpret_cast<const f32x4*>(wl + kk * 32);
-            const float v = xv[kk];
-#pragma unroll
-            for (int n4 = 0; n4 < 8; ++n4) {
-                const f32x4 wv = wp[n4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[n4 * 4 + e] = fmaf(v, wv[e], acc[n4 * 4 + e]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int n = 0; n < 32; ++n) {
-        float v = acc[n];
-        if (n < g.Cout) {
-            v = v * (g.scale ? g.scale[n] : 1.f) + (g.shift ? g.shift[n] : 0.f);
-            v = y4_act(v, g.act);
-        }
-        tile[wave][lane][n] = v;
-    }
-    __syncthreads();
-    // 64 pixels x 32 ch: lane -> (pixel = it*2 + lane/32, ch = lane%32): 128-B contiguous per half wave
-    const int ch = lane & 31;
-    if (ch < g.Cout) {
-#pragma unroll 4
-        for (int it = 0; it < 32; ++it) {
-            const int pl = it * 2 + (lane >> 5);
-            const long long p = pix0 + pl;
-            if (p < g.M) g.y[p * g.ldy + ch] = tile[wave][pl][ch];
-        }
-    }
-    if (g.stats) {                                   // uniform branch: column sums of this block's 256 pixels
-        __shared__ float sred[8][32][2];
-        const int grp = tid >> 5;                    // 8 groups of 32 pixels
-        float cs = 0.f, css = 0.f;
-        for (int i = 0; i < 32; ++i) { const float v = tile[grp >> 1][(grp & 1) * 32 + i][ch]; cs += v; css += v * v; }
-        sred[grp][ch][0] = cs; sred[grp][ch][1] = css;
-        __syncthreads();
-        if (tid < 64) {
-            const int c = tid & 31, which = tid >> 5;
-            float t = 0.f;
-            for (int k = 0; k < 8; ++k) t += sred[k][c][which];
-            if (c < g.Cout) g.stats[((long long)blockIdx.x * 2 + which) * g.Cout + c] = t;
-        }
-    }
+template <int NP>
+int wgrad_tiles(const WgradGeom& g, hipStream_t st) {
+    if (g.tn == 128 && g.tj == 128) return launch_wgrad<128, 128, NP>(g, st);
+    if (g.tn == 128) return launch_wgrad<128, 64, NP>(g, st);
+    if (g.tj == 128) return launch_wgrad<64, 128, NP>(g, st);
+    return launch_wgrad<64, 64, NP>(g, st);
 }
-
-// Stem forward on the matrix cores (bf16x3 mode): the 27-value patch of a pixel is the A row (K = 27 -> 32,
-// ordered k = r*9 + c*3 + q so that the three q of one (r, c) are neighbours in memory), gathered straight from
-// the strided input into the MFMA A layout (lane = pixel, 2 x 8 k values), split in registers; the filter is
-// 24 VGPRs of B fragments per wave.  12 MFMAs per 32 pixels x 32 channels; the C layout (lane = channel) gives
-// 128-byte contiguous stores.  Persistent blocks walk groups of 256 pixels and leave one BN-statistics row
-// per group (same contract as the VALU kernel above).
-__global__ __launch_bounds__(256) void conv_stem_fwd_bf16x3_kernel(const StemGeom g, const int ngroups, const float inv_hw,
-                                                                   const float inv_w) {
-    __shared__ float sred[4][32][2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fr = lane & 31, fh = lane >> 5;
-    const int HW = g.H * g.W;
-    bf16x8 fb[2][3];
-    int koff[16];          // element offset of k relative to the pixel, per lane
-    int ktap[16];          // r*3+q (bit index into the 9-bit validity mask), 9 = padding k
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int k = (i >> 3) * 16 + fh * 8 + (i & 7);
-        const int r = k / 9, c = (k - r * 9) / 3, q = k - r * 9 - c * 3;
-        const bool kv = k < 27;
-        koff[i] = kv ? (int)(c * g.sxc + (r - 1) * g.sxh + (q - 1) * g.sxw) * 4 : 0;
-        ktap[i] = kv ? r * 3 + q : 9;
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        f32x4 w0, w1;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int k = ks * 16 + fh * 8 + i;
-            const int r = k / 9, c = (k - r * 9) / 3, q = k - r * 9 - c * 3;
-            const float v = (k < 27 && fr < g.Cout) ? g.w[fr * 27 + (r * 3 + q) * 3 + c] : 0.f;
-            if (i < 4) w0[i] = v; else w1[i - 4] = v;
-        }
-        u32x2 a1, a2, a3, b1, b2, b3;
-        split3x4(w0, a1, a2, a3);
-        split3x4(w1, b1, b2, b3);
-        const u32x4 q1 = {a1[0], a1[1], b1[0], b1[1]}, q2 = {a2[0], a2[1], b2[0], b2[1]}, q3 = {a3[0], a3[1], b3[0], b3[1]};
-        fb[ks][0] = __builtin_bit_cast(bf16x8, q1); fb[ks][1] = __builtin_bit_cast(bf16x8, q2); fb[ks][2] = __builtin_bit_cast(bf16x8, q3);
-    }
-    const float sc = (g.scale && fr < g.Cout) ? g.scale[fr] : 1.f;
-    const float sh = (g.shift && fr < g.Cout) ? g.shift[fr] : 0.f;
-    const __amdgpu_buffer_rsrc_t rsrc = y4_make_rsrc(g.x, 0xfffffff0u);      // extent checked on the host
-    float xv0[16], xv1[16];
-    auto load = [&](float (&xv)[16], long long tile) {
-        const long long p = tile * 32 + fr;
-        unsigned base = 0xffffffffu;
-        unsigned m9 = 0;
-        if (p < g.M) {
-            int b = (int)((float)p * inv_hw);
-            int rem = (int)(p - (long long)b * HW);
-            if (rem < 0) { --b; rem += HW; } else if (rem >= HW) { ++b; rem -= HW; }
-            int h = (int)((float)rem * inv_w);
-            int w = rem - h * g.W;
-            if (w < 0) { --h; w += g.W; } else if (w >= g.W) { ++h; w -= g.W; }
-            base = (unsigned)(b * g.sxb + h * g.sxh + w * g.sxw) * 4u;
-            const unsigned hm = (h > 0 ? 1u : 0u) | 2u | (h + 1 < g.H ? 4u : 0u);
-            const unsigned wm = (w > 0 ? 1u : 0u) | 2u | (w + 1 < g.W ? 4u : 0u);
-            m9 = ((hm & 1u) ? wm : 0u) | ((hm & 2u) ? wm << 3 : 0u) | ((hm & 4u) ? wm << 6 : 0u);
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const bool ok = (m9 >> ktap[i]) & 1u;
-            xv[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, ok ? (int)(base + (unsigned)koff[i]) : -1, 0, 0));
-        }
-    };
-    float cs = 0.f, css = 0.f;
-    auto compute = [&](float (&xv)[16], long long tile) {
-        f32x16 acc;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const f32x4 v0 = {xv[ks * 8 + 0], xv[ks * 8 + 1], xv[ks * 8 + 2], xv[ks * 8 + 3]};
-            const f32x4 v1 = {xv[ks * 8 + 4], xv[ks * 8 + 5], xv[ks * 8 + 6], xv[ks * 8 + 7]};
-            u32x2 a1, a2, a3, b1, b2, b3;
-            split3x4(v0, a1, a2, a3);
-            split3x4(v1, b1, b2, b3);
-            const u32x4 q1 = {a1[0], a1[1], b1[0], b1[1]}, q2 = {a2[0], a2[1], b2[0], b2[1]}, q3 = {a3[0], a3[1], b3[0], b3[1]};
-            const bf16x8 f1 = __builtin_bit_cast(bf16x8, q1), f2 = __builtin_bit_cast(bf16x8, q2), f3 = __builtin_bit_cast(bf16x8, q3);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f3, fb[ks][0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2, fb[ks][1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f1, fb[ks][2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2, fb[ks][0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f1, fb[ks][1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f1, fb[ks][0], acc, 0, 0, 0);
-        }
-        const long long mbase = tile * 32 + 4 * fh;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float raw = acc[e];
-            cs += raw; css += raw * raw;                  // pixels past M contribute exact zeros
-            const long long m = mbase + (e & 3) + 8 * (e >> 2);
-            if (fr < g.Cout && m < g.M) g.y[m * g.ldy + fr] = y4_act(raw * sc + sh, g.act);
-        }
-    };
-    for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const long long t0 = (long long)grp * 8 + wave * 2;
-        load(xv0, t0);
-        load(xv1, t0 + 1);
-        cs = 0.f; css = 0.f;
-        compute(xv0, t0);
-        compute(xv1, t0 + 1);
-        if (g.stats) {
-            cs += __shfl_xor(cs, 32, 64);
-            css += __shfl_xor(css, 32, 64);
-            if (fh == 0) { sred[wave][fr][0] = cs; sred[wave][fr][1] = css; }
-            __syncthreads();
-            if (tid < 64) {
-                const int c = tid & 31, which = tid >> 5;
-                const float t = (sred[0][c][which] + sred[1][c][which]) + (sred[2][c][which] + sred[3][c][which]);
-                if (c < g.Cout) g.stats[((long long)grp * 2 + which) * g.Cout + c] = t;
-            }
-            __syncthreads();
-        }
-    }
-}
-
-// wgrad of the stem: D[n][j] (32 x 27->32) = sum_p dy[p][n] * x[p + tap(j)][c(j)], operands
-// straight from global memory into the MFMA (a dy pixel row IS the 32-float A fragment).
-struct StemWgradGeom {
-    const float* x; const float* dy; float* slabs;
-    long long sxb, sxc, sxh, sxw, lddy;
-    int B, H, W, Cout;
-    long long M, pix_per_wave;
-};
-
-__global__ __launch_bounds__(256) void conv_stem_wgrad_kernel(const StemWgradGeom g) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const long long wave_id = (long long)blockIdx.x * 4 + (tid >> 6);
-    const long long p_begin = wave_id * g.pix_per_wave;
-    long long p_end = p_begin + g.pix_per_wave;
-    if (p_end > g.M) p_end = g.M;
-    const int fr = lane & 31, fh = lane >> 5;
-    const bool jok = fr < 27;
-    const int tap = jok ? fr / 3 : 0, c = jok ? fr - tap * 3 : 0;
-    const int r = tap / 3 - 1, q = tap - (tap / 3) * 3 - 1;
-    const bool nok = fr < g.Cout;
-    f32x16 acc;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-    // running (b, h, w) of this lane's pixel p = p_begin + fh + 2*iter: no divisions in the loop
-    long long p = p_begin + fh;
-    int b = 0, h = 0, w = 0;
-    if (p < g.M) {
-        b = (int)(p / ((long long)g.H * g.W));
-        const int rem = (int)(p - (long long)b * g.H * g.W);
-        h = rem / g.W; w = rem - h * g.W;
-    }
-    // 8 pixel pairs per trip: 16 independent buffer loads (out-of-range / halo lanes read zeros through the
-    // descriptor's bounds check) are in flight before the 8 MFMAs consume them -- the loop is latency-bound otherwise
-    const long long dy_first = p_begin < g.M ? p_begin : 0;
-    const __amdgpu_buffer_rsrc_t dy_rsrc = y4_make_rsrc(g.dy + dy_first * g.lddy, (unsigned)(g.pix_per_wave * g.lddy * 4));
-    const __amdgpu_buffer_rsrc_t x_rsrc = y4_make_rsrc(g.x, 0xfffffff0u);                     // extent checked on the host
-    const unsigned dy_step = (unsigned)g.lddy * 8u;                                            // 2 pixels
-    unsigned dy_off = ((unsigned)fh * (unsigned)g.lddy + (unsigned)fr) * 4u;
-    const long long coff = c * g.sxc;
-    for (long long pc = p_begin; pc < p_end; pc += 16) {
-        float a[8], bv[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const bool pok = p < p_end;
-            const int hi = h + r, wi = w + q;
-            const bool xok = pok && jok && (unsigned)hi < (unsigned)g.H && (unsigned)wi < (unsigned)g.W;
-            const unsigned xo = (unsigned)(b * g.sxb + coff + hi * g.sxh + wi * g.sxw) * 4u;
-            a[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dy_rsrc, (pok && nok) ? (int)dy_off : -1, 0, 0));
-            bv[u] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(x_rsrc, xok ? (int)xo : -1, 0, 0));
-            dy_off += dy_step;
-            p += 2;
-            w += 2;
-            if (w >= g.W) { w -= g.W; if (++h == g.H) { h = 0; ++b; } }  // W >= 2
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], bv[u], acc, 0, 0, 0);
-    }
-    float* out = g.slabs + wave_id * 1024;     // [32 n][32 j]
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int n = (e & 3) + 8 * (e >> 2) + 4 * fh;
-        out[n * 32 + fr] = acc[e];
-    }
-}
-
-// Two coalesced stages over the per-wave slabs [nslabs][32 n][32 j]: 64 blocks each fold nslabs/64 slabs for all
-// 1024 entries (thread <-> 4 consecutive entries, fp64), then one block folds the 64 partial rows in a fixed order.
-__global__ __launch_bounds__(256) void stem_wgrad_reduce1_kernel(const float* __restrict__ slabs, double* __restrict__ part,
-                                                                 int nslabs) {
-    const int per = (nslabs + gridDim.x - 1) / gridDim.x;
-    const int k0 = blockIdx.x * per;
-    const int k1 = min(nslabs, k0 + per);
-    double s[4] = {0, 0, 0, 0};
-    for (int k = k0; k < k1; ++k) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(slabs + (long long)k * 1024 + threadIdx.x * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) s[e] += (double)v[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) part[(long long)blockIdx.x * 1024 + threadIdx.x * 4 + e] = s[e];
-}
-__global__ __launch_bounds__(256) void stem_wgrad_reduce2_kernel(const double* __restrict__ part, float* __restrict__ dw,
-                                                                 int nparts, int Cout) {
-    for (int i = threadIdx.x; i < Cout * 27; i += 256) {
-        const int n = i / 27, j = i - n * 27;
-        double s = 0.0;
-        for (int k = 0; k < nparts; ++k) s += part[(long long)k * 1024 + n * 32 + j];
-        dw[i] = (float)s;
-    }
-}
-
-constexpr int STEM_WAVES = 4096;
 
 }  // namespace
 
+// ---------------------------------------------------------------- what conv_api.hip calls (declared in conv_geom.h)
 namespace y4 {
-// the two fold launches of y4_conv2d_stem_wgrad_f32 over another producer's slabs (stem_fused.hip)
-int stem_wgrad_fold(const float* slabs, int nslabs, double* part, float* dw, int Cout, hipStream_t st) {
-    hipLaunchKernelGGL(stem_wgrad_reduce1_kernel, dim3(64), dim3(256), 0, st, slabs, part, nslabs);
-    Y4_CHECK_LAUNCH();
-    hipLaunchKernelGGL(stem_wgrad_reduce2_kernel, dim3(1), dim3(256), 0, st, part, dw, 64, Cout);
-    Y4_CHECK_LAUNCH();
-    return Y4_OK;
-}
-int slab_reduce(const float* slabs, float* dw, long long n, int splits, hipStream_t st) {
-    if ((n & 3) == 0 && !(reinterpret_cast<uintptr_t>(dw) & 15) && !(reinterpret_cast<uintptr_t>(slabs) & 15)) {
-        const long long nvec = n / 4;
-        if (nvec >= 64 * 1024)
-            hipLaunchKernelGGL(slab_reduce_vec_kernel<64>, dim3((unsigned)((nvec + 63) / 64)), dim3(256), 0, st,
-                               reinterpret_cast<const f32x4*>(slabs), reinterpret_cast<f32x4*>(dw), nvec, splits);
-        else
-            hipLaunchKernelGGL(slab_reduce_vec_kernel<16>, dim3((unsigned)((nvec + 15) / 16)), dim3(256), 0, st,
-                               reinterpret_cast<const f32x4*>(slabs), reinterpret_cast<f32x4*>(dw), nvec, splits);
-    } else {
-        const int blocks = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-        hipLaunchKernelGGL(slab_reduce_kernel, dim3(blocks), dim3(256), 0, st, slabs, dw, n, splits);
-    }
-    Y4_CHECK_LAUNCH();
-    return Y4_OK;
-}
-}  // namespace y4
 
-// ======================================================================================== C ABI
-extern "C" {
-
-int y4_set_conv_mode(int mode) {
-    if (mode < 0 || mode > 3) return Y4_ERR_SHAPE;
-    g_conv_mode = mode;
-    return Y4_OK;
-}
-int y4_get_conv_mode(void) { return g_conv_mode; }
-
-// Per-call workspace of the forward conv (modes 1-3): [64 B of amax words: [0] filter, [1] gathered tensor when the caller
-// gave none][4 KiB of per-block filter maxima][filter planes].  Nothing is shared between calls, so convs may be issued
-// from any number of streams / devices / threads at once.
-constexpr size_t FWD_WS_HDR = 64 + 4096;
-
-size_t y4_conv2d_fwd_workspace(int Cin, int Cout, int k) {
-    if (Cin <= 0 || Cout <= 0 || k <= 0) return 0;
-    return FWD_WS_HDR + (size_t)Cout * k * k * Cin * 6;
-}
-
-static int conv_fwd_impl(const float* x, int ldx, const float* w, float* y, int ldy,
-                         int B, int H, int W, int Cin, int Cout, int k, int stride,
-                         const float* scale, const float* shift, int act,
-                         const float* residual, int ldr, float* stats, int* nparts, const unsigned* x_amax,
-                         unsigned* y_amax, void* workspace, size_t workspace_bytes, void* stream,
-                         void* w_prepared = nullptr, void* dgrad_filter = nullptr, size_t dgrad_filter_bytes = 0) {
-    if (!x || (!w && !w_prepared) || !y) return Y4_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (k != 1 && k != 3) || (stride != 1 && stride != 2))
-        return Y4_ERR_SHAPE;
-    if (Cin <= 0 || Cin % BK != 0 || ldx < Cin || ldy < Cout || (ldx & 3) || (residual && ldr < Cout))
-        return Y4_ERR_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(w) & 15)) return Y4_ERR_SHAPE;
-    const int pad = (k - 1) / 2;
-    ConvGeom g{};
-    g.src = x; g.wt = w; g.dst = y; g.scale = scale; g.shift = shift; g.res = residual; g.stats = stats;
-    g.lds_ = ldx; g.ldd = ldy; g.ldr = ldr;
-    g.B = B; g.Hs = H; g.Ws = W; g.Cs = Cin; g.Cs_valid = Cin;
-    g.Hd = (H + 2 * pad - k) / stride + 1;
-    g.Wd = (W + 2 * pad - k) / stride + 1;
-    g.N = Cout; g.k = k; g.stride = stride; g.pad = pad;
-    const long long M = (long long)B * g.Hd * g.Wd;
-    if (M >= (1ll << 31)) return Y4_ERR_SHAPE;
-    g.M = (int)M; g.K = k * k * Cin; g.act = act;
-    if (w_prepared) {
-        // filter already split (y4_conv2d_prepare_filter_f32): [word 0: max|w| bits][word 1: scratch][.. 64 B][4 KiB][planes]
-        if (g_conv_mode != 3) return Y4_ERR_SHAPE;
-        if (reinterpret_cast<uintptr_t>(w_prepared) & 15) return Y4_ERR_SHAPE;
-        unsigned* hdr = static_cast<unsigned*>(w_prepared);
-        g.wt_planes = reinterpret_cast<unsigned short*>(static_cast<char*>(w_prepared) + 64 + 4096);
-        if (!x_amax) {
-            const int rc = y4::amax_launch(x, ldx, (long long)B * H * W, Cin, hdr + 1, y4_stream(stream));
-            if (rc != Y4_OK) return rc;
-            x_amax = hdr + 1;
-        }
-        g.src_amax = x_amax; g.wt_amax = hdr; g.dst_amax = y_amax;
-        return y4::f16x2_gather(g, false, y4_stream(stream), nparts);
-    }
-    if (g_conv_mode != 0) {
-        const long long nw = (long long)Cout * g.K;
-        if (!workspace) return Y4_ERR_NULL;
-        if (workspace_bytes < y4_conv2d_fwd_workspace(Cin, Cout, k)) return Y4_ERR_WORKSPACE;
-        if (reinterpret_cast<uintptr_t>(workspace) & 15) return Y4_ERR_SHAPE;
-        unsigned* hdr = static_cast<unsigned*>(workspace);
-        unsigned short* planes = reinterpret_cast<unsigned short*>(static_cast<char*>(workspace) + FWD_WS_HDR);
-        g.wt_planes = planes;
-        if (g_conv_mode == 3) {
-            int rc;
-            if (dgrad_filter) {
-                // the backward pass of this layer will want the transposed planes of the same filter: both in one launch,
-                // into a buffer laid out as y4_conv2d_dgrad_f32's workspace (which that call then takes with w == NULL)
-                if (dgrad_filter_bytes < y4_conv2d_dgrad_workspace(Cin, Cout, k)) return Y4_ERR_WORKSPACE;
-                if (reinterpret_cast<uintptr_t>(dgrad_filter) & 15) return Y4_ERR_SHAPE;
-                const int cp = (Cout + 31) / 32 * 32;
-                unsigned* hdr_t = reinterpret_cast<unsigned*>(static_cast<char*>(dgrad_filter) + (size_t)Cin * k * k * cp * 6);
-                // (the 2-D tile kernel runs dgrad in forward form: it wants the taps mirrored; same test as in conv_dgrad_impl)
-                rc = y4::f16x2_filter_planes_dual(w, planes, hdr, hdr + 16, static_cast<unsigned short*>(dgrad_filter), hdr_t, Cout, Cin,
-                                                  k * k, cp, y4::tile_conv_ok(cp, Cout, Cin, k, stride, H, W), y4_stream(stream));
-            } else {
-                rc = y4::f16x2_filter_planes(w, planes, Cout, g.K, hdr, hdr + 16, y4_stream(stream));
-            }
-            if (rc != Y4_OK) return rc;
-            if (!x_amax) {                                  // no producer-side maximum: one extra pass over the input
-                rc = y4::amax_launch(x, ldx, (long long)B * H * W, Cin, hdr + 1, y4_stream(stream));
-                if (rc != Y4_OK) return rc;
-                x_amax = hdr + 1;
-            }
-            g.src_amax = x_amax; g.wt_amax = hdr; g.dst_amax = y_amax;
-            return y4::f16x2_gather(g, false, y4_stream(stream), nparts);
-        }
-        const int blocks = (int)((nw + 255) / 256 > 4096 ? 4096 : (nw + 255) / 256);
-        hipLaunchKernelGGL(split_filter_kernel, dim3(blocks), dim3(256), 0, y4_stream(stream), w, planes, nw,
-                           g_conv_mode == 2 ? 1 : 3);
-        Y4_CHECK_LAUNCH();
-    }
-    return dispatch_gather<false>(g, y4_stream(stream), nparts);
-}
-
-int y4_conv2d_fwd_f32(const float* x, int ldx, const float* w, float* y, int ldy,
-                      int B, int H, int W, int Cin, int Cout, int k, int stride,
-                      const float* scale, const float* shift, int act,
-                      const float* residual, int ldr, const unsigned* x_amax, unsigned* y_amax,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-    return conv_fwd_impl(x, ldx, w, y, ldy, B, H, W, Cin, Cout, k, stride, scale, shift, act, residual, ldr, nullptr,
-                         nullptr, x_amax, y_amax, workspace, workspace_bytes, stream);
-}
-
-int y4_amax_f32(const float* x, int ldx, long long M, int C, unsigned* amax_bits, void* stream) {
-    if (!x || !amax_bits) return Y4_ERR_NULL;
-    if (M < 0 || C <= 0 || ldx < C) return Y4_ERR_SHAPE;
-    return y4::amax_launch(x, ldx, M, C, amax_bits, y4_stream(stream));
-}
-
-int y4_amax_merge_u32(unsigned* dst, const unsigned* src, void* stream) {
-    if (!dst || !src) return Y4_ERR_NULL;
-    return y4::amax_merge(dst, src, y4_stream(stream));
-}
-
-size_t y4_conv2d_bnstats_workspace(int B, int H, int W, int Cin, int Cout, int k, int stride) {
-    if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (k != 1 && k != 3) || (stride != 1 && stride != 2)) return 0;
-    const int pad = (k - 1) / 2;
-    const long long M = (long long)B * ((H + 2 * pad - k) / stride + 1) * ((W + 2 * pad - k) / stride + 1);
-    long long rows = Cin == 3 ? (M + 255) / 256 : (M + 63) / 64;            // smallest M-tile of any variant
-    const long long per_img = (long long)B * ((M / B + 127) / 128);         // the 3x3 halo kernel tiles image by image
-    if (per_img > rows) rows = per_img;
-    return (size_t)rows * 2 * Cout * sizeof(float);
-}
-
-int y4_conv2d_fwd_bnstats_f32(const float* x, int ldx, const float* w, float* y, int ldy,
-                              int B, int H, int W, int Cin, int Cout, int k, int stride,
-                              float* partials, size_t partial_bytes, long long* nparts_host, const unsigned* x_amax,
-                              void* workspace, size_t workspace_bytes, void* dgrad_filter, size_t dgrad_filter_bytes,
-                              void* stream) {
-    if (!partials || !nparts_host) return Y4_ERR_NULL;
-    if (dgrad_filter && g_conv_mode != 3) return Y4_ERR_SHAPE;
-    if (partial_bytes < y4_conv2d_bnstats_workspace(B, H, W, Cin, Cout, k, stride)) return Y4_ERR_WORKSPACE;
-    int np = 0;
-    const int rc = conv_fwd_impl(x, ldx, w, y, ldy, B, H, W, Cin, Cout, k, stride, nullptr, nullptr, Y4_ACT_LINEAR,
-                                 nullptr, 0, partials, &np, x_amax, nullptr, workspace, workspace_bytes, stream, nullptr,
-                                 dgrad_filter, dgrad_filter_bytes);
-    if (rc != Y4_OK) return rc;
-    *nparts_host = np;
-    return Y4_OK;
-}
-
-size_t y4_conv2d_dgrad_workspace(int Cin, int Cout, int k) {
-    const size_t cp = (size_t)((Cout + 31) / 32) * 32;
-    // fp32 transposed filter (4 B), 3 bf16 planes (6 B) or 2 fp16 planes (4 B) per element, + 64 B of amax words
-    // + 4 KiB of per-block filter maxima
-    return (size_t)Cin * k * k * cp * 6 + 64 + 4096;
-}
-
-static int conv_dgrad_impl(const float* dy, int lddy, const float* w, float* dx, int lddx,
-                           int B, int H, int W, int Cin, int Cout, int k, int stride,
-                           void* workspace, size_t workspace_bytes, const unsigned* dy_amax,
-                           const float* residual, int ldr, void* stream) {
-    if (!dy || !dx || !workspace) return Y4_ERR_NULL;
-    if (!w && g_conv_mode != 3) return Y4_ERR_NULL;        // w == NULL: the workspace already holds the transposed planes
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (k != 1 && k != 3) || (stride != 1 && stride != 2))
-        return Y4_ERR_SHAPE;
-    const int Cout_pad = (Cout + 31) / 32 * 32;
-    // the padded channels of dy are read (multiplied by zero filter rows): they must exist
-    if (lddy < Cout_pad || (lddy & 3) || lddx < Cin) return Y4_ERR_SHAPE;
-    if (workspace_bytes < y4_conv2d_dgrad_workspace(Cin, Cout, k)) return Y4_ERR_WORKSPACE;
-    if ((reinterpret_cast<uintptr_t>(dy) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return Y4_ERR_SHAPE;
-    hipStream_t st = y4_stream(stream);
-    float* wt = static_cast<float*>(workspace);
-    const long long total = (long long)Cin * k * k * Cout_pad;
-    const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    unsigned* hdr = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + (size_t)total * 6);
-    unsigned* wamax = hdr;                                 // the call's own words: nothing shared between calls
-    if (g_conv_mode == 3) {
-        if (w) {
-            const int rc = y4::f16x2_filter_planes_transposed(w, static_cast<unsigned short*>(workspace), Cout, Cin, k * k, Cout_pad,
-                                                              wamax, hdr + 16, st, y4::tile_conv_ok(Cout_pad, Cout, Cin, k, stride, H, W));
-            if (rc != Y4_OK) return rc;
-        }                                                  // else: left there by y4_conv2d_fwd_bnstats_f32(..., dgrad_filter)
-    } else if (g_conv_mode != 0)
-        hipLaunchKernelGGL(transpose_split_filter_kernel, dim3(blocks), dim3(256), 0, st, w,
-                           static_cast<unsigned short*>(workspace), Cout, Cin, k * k, Cout_pad, g_conv_mode == 2 ? 1 : 3);
+int igemm_filter(int mode, const float* w, void* out, int Cout, int Cin, int kk, bool transposed, hipStream_t st) {
+    const int np = mode == 2 ? 1 : 3, Cout_pad = (Cout + 31) / 32 * 32;
+    const long long n = (long long)Cin * kk * (transposed ? Cout_pad : Cout);
+    const int blocks = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
+    unsigned short* planes = static_cast<unsigned short*>(out);
+    if (!transposed)
+        hipLaunchKernelGGL(split_filter_kernel, dim3(blocks), dim3(256), 0, st, w, planes, n, np);
+    else if (mode != 0)
+        hipLaunchKernelGGL(transpose_split_filter_kernel, dim3(blocks), dim3(256), 0, st, w, planes, Cout, Cin, kk, Cout_pad, np);
     else
-        hipLaunchKernelGGL(transpose_filter_kernel, dim3(blocks), dim3(256), 0, st, w, wt, Cout, Cin, k * k, Cout_pad);
-    Y4_CHECK_LAUNCH();
-    const int pad = (k - 1) / 2;
-    ConvGeom g{};
-    if (residual && ldr < Cin) return Y4_ERR_SHAPE;
-    g.src = dy; g.wt = wt; g.dst = dx; g.scale = nullptr; g.shift = nullptr; g.res = residual;
-    g.wt_planes = static_cast<const unsigned short*>(workspace);
-    g.lds_ = lddy; g.ldd = lddx; g.ldr = ldr;
-    g.B = B;
-    g.Hs = (H + 2 * pad - k) / stride + 1;
-    g.Ws = (W + 2 * pad - k) / stride + 1;
-    g.Cs = Cout_pad; g.Cs_valid = Cout;
-    g.Hd = H; g.Wd = W; g.N = Cin; g.k = k; g.stride = stride; g.pad = pad;
-    const long long M = (long long)B * H * W;
-    if (M >= (1ll << 31)) return Y4_ERR_SHAPE;
-    g.M = (int)M; g.K = k * k * Cout_pad; g.act = Y4_ACT_LINEAR;
-    if (g_conv_mode == 3) {
-        if (!dy_amax) {
-            // pad channels of dy may hold anything: the maximum is taken over the valid channels only
-            const int rc = y4::amax_launch(dy, lddy, (long long)B * g.Hs * g.Ws, Cout, hdr + 1, st);
-            if (rc != Y4_OK) return rc;
-            dy_amax = hdr + 1;
-        }
-        g.src_amax = dy_amax; g.wt_amax = wamax;
-        // few channels on a large map: the 2-D tile kernel, in forward form on the mirrored transposed planes (above)
-        if (y4::tile_conv_ok(Cout_pad, Cout, Cin, k, stride, H, W)) return y4::f16x2_tile(g, st, nullptr);
-        if (y4::tile_dgrad_s2_ok(Cout_pad, Cout, Cin, k, stride, g.Hs, g.Ws)) return y4::f16x2_tile_dgrad_s2(g, st);
-        return y4::f16x2_gather(g, true, st, nullptr);
-    }
-    return dispatch_gather<true>(g, st);
-}
-
-int y4_conv2d_dgrad_f32(const float* dy, int lddy, const float* w, float* dx, int lddx,
-                        int B, int H, int W, int Cin, int Cout, int k, int stride,
-                        void* workspace, size_t workspace_bytes, const unsigned* dy_amax,
-                        const float* residual, int ldr, void* stream) {
-    return conv_dgrad_impl(dy, lddy, w, dx, lddx, B, H, W, Cin, Cout, k, stride, workspace, workspace_bytes, dy_amax,
-                           residual, ldr, stream);
-}
-
-int y4_last_conv_kernel(char* buf, int cap) {
-    if (!buf || cap <= 0) return Y4_ERR_NULL;
-    snprintf(buf, (size_t)cap, "%s", g_last_kernel);
-    g_last_kernel[0] = 0;
-    return Y4_OK;
-}
-
-size_t y4_conv2d_prepared_bytes(int Cout, int K) {
-    if (Cout <= 0 || K <= 0) return 0;
-    return 64 + 4096 + (size_t)Cout * (size_t)K * 4;
-}
-
-int y4_conv2d_prepare_filter_f32(const float* w, int Cout, int K, void* prepared, size_t prepared_bytes, void* stream) {
-    if (!w || !prepared) return Y4_ERR_NULL;
-    if (Cout <= 0 || K <= 0 || (K & 31)) return Y4_ERR_SHAPE;
-    if (prepared_bytes < y4_conv2d_prepared_bytes(Cout, K)) return Y4_ERR_WORKSPACE;
-    if ((reinterpret_cast<uintptr_t>(prepared) & 15) || (reinterpret_cast<uintptr_t>(w) & 15)) return Y4_ERR_SHAPE;
-    return y4::f16x2_refresh_prepared(w, prepared, Cout, K, y4_stream(stream));
-}
-
-int y4_conv2d_fwd_prepared_f32(const float* x, int ldx, void* w_prepared, float* y, int ldy,
-                               int B, int H, int W, int Cin, int Cout, int k, int stride,
-                               const float* scale, const float* shift, int act,
-                               const float* residual, int ldr, const unsigned* x_amax, unsigned* y_amax, void* stream) {
-    if (!w_prepared) return Y4_ERR_NULL;
-    return conv_fwd_impl(x, ldx, nullptr, y, ldy, B, H, W, Cin, Cout, k, stride, scale, shift, act, residual, ldr, nullptr,
-                         nullptr, x_amax, y_amax, nullptr, 0, stream, w_prepared);
-}
-
-size_t y4_conv2d_wgrad_workspace(int B, int H, int W, int Cin, int Cout, int k, int stride) {
-    WgradGeom g{};
-    wgrad_plan(B, H, W, Cin, Cout, k, stride, g);
-    // slabs of the split-K partial sums + 64 B of amax words (f16x2 mode); the tile kernel (wgrad_tile.hip) writes one slab per block
-    int splits = g.splits;
-    if (y4::tile_wgrad_ok(Cin, Cout, k, stride, H, W, 0, 0) && y4::tile_wgrad_slabs(Cin, Cout) > splits) splits = y4::tile_wgrad_slabs(Cin, Cout);
-    return (splits > 1 ? (size_t)splits * Cout * g.J * sizeof(float) : 0) + 64;
-}
-
-int y4_conv2d_wgrad_f32(const float* x, int ldx, const float* dy, int lddy, float* dw,
-                        int B, int H, int W, int Cin, int Cout, int k, int stride,
-                        void* workspace, size_t workspace_bytes, const unsigned* x_amax, const unsigned* dy_amax,
-                        void* stream) {
-    if (!x || !dy || !dw) return Y4_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || (k != 1 && k != 3) || (stride != 1 && stride != 2))
-        return Y4_ERR_SHAPE;
-    if (Cin <= 0 || (Cin & 3) || ldx < Cin || (ldx & 3) || (lddy & 3) || lddy < ((Cout + 3) & ~3)) return Y4_ERR_SHAPE;
-    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(dy) & 15)) return Y4_ERR_SHAPE;
-    WgradGeom g{};
-    wgrad_plan(B, H, W, Cin, Cout, k, stride, g);
-    if ((long long)B * g.Ho * g.Wo >= (1ll << 31)) return Y4_ERR_SHAPE;
-    g.x = x; g.dy = dy; g.ldx = ldx; g.lddy = lddy;
-    {
-        g.x_total_bytes = (unsigned long long)B * H * W * (unsigned long long)ldx * 4ull;
-        g.dy_total_bytes = (unsigned long long)B * g.Ho * g.Wo * (unsigned long long)lddy * 4ull;
-        const unsigned long long range_px = (unsigned long long)g.chunks_per_split * 32ull + 2ull * g.Ho * g.Wo;
-        const unsigned long long per_px = 4ull * (unsigned long long)(lddy > ldx * stride * stride ? lddy : ldx * stride * stride);
-        if (range_px * per_px >= 0xfffffff0ull) return Y4_ERR_SHAPE;      // pitch more than 2x the channel count at > 4 GiB
-    }
-    hipStream_t st = y4_stream(stream);
-    // few channels on a large map (3x3): the tile kernel -- every x pixel staged once for nine taps, one slab per block
-    const bool tile = g_conv_mode == 3 && y4::tile_wgrad_ok(Cin, Cout, k, stride, H, W, ldx, lddy);
-    if (tile) g.splits = y4::tile_wgrad_slabs(Cin, Cout);
-    const size_t slab_bytes = g.splits > 1 ? (size_t)g.splits * Cout * g.J * sizeof(float) : 0;
-    if (g.splits > 1) {
-        if (!workspace) return Y4_ERR_NULL;
-        if (workspace_bytes < slab_bytes) return Y4_ERR_WORKSPACE;
-        g.out = static_cast<float*>(workspace);
-    } else {
-        g.out = dw;
-    }
-    int rc;
-    if (g_conv_mode == 3) {
-        if (!x_amax || !dy_amax) {
-            if (!workspace || workspace_bytes < slab_bytes + 64) return Y4_ERR_WORKSPACE;
-            unsigned* hdr = reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + slab_bytes);
-            if (!x_amax) {
-                rc = y4::amax_launch(x, ldx, (long long)B * H * W, Cin, hdr, st);
-                if (rc != Y4_OK) return rc;
-                x_amax = hdr;
-            }
-            if (!dy_amax) {
-                rc = y4::amax_launch(dy, lddy, (long long)B * g.Ho * g.Wo, Cout, hdr + 1, st);
-                if (rc != Y4_OK) return rc;
-                dy_amax = hdr + 1;
-            }
-        }
-        g.x_amax = x_amax; g.dy_amax = dy_amax;
-        rc = tile ? y4::f16x2_wgrad_tile(g, st) : y4::f16x2_wgrad(g, st);
-    } else if (g_conv_mode == 1) {
-        if (g.tn == 128 && g.tj == 128) rc = launch_wgrad<128, 128, 3>(g, st);
-        else if (g.tn == 128) rc = launch_wgrad<128, 64, 3>(g, st);
-        else if (g.tj == 128) rc = launch_wgrad<64, 128, 3>(g, st);
-        else rc = launch_wgrad<64, 64, 3>(g, st);
-    } else if (g_conv_mode == 2) {
-        if (g.tn == 128 && g.tj == 128) rc = launch_wgrad<128, 128, 1>(g, st);
-        else if (g.tn == 128) rc = launch_wgrad<128, 64, 1>(g, st);
-        else if (g.tj == 128) rc = launch_wgrad<64, 128, 1>(g, st);
-        else rc = launch_wgrad<64, 64, 1>(g, st);
-    } else if (g.tn == 128 && g.tj == 128) rc = launch_wgrad<128, 128>(g, st);
-    else if (g.tn == 128) rc = launch_wgrad<128, 64>(g, st);
-    else if (g.tj == 128) rc = launch_wgrad<64, 128>(g, st);
-    else rc = launch_wgrad<64, 64>(g, st);
-    if (rc != Y4_OK) return rc;
-    if (g.splits > 1) {
-        const int rc2 = y4::slab_reduce(static_cast<const float*>(workspace), dw, (long long)Cout * g.J, g.splits, st);
-        if (rc2 != Y4_OK) return rc2;
-    }
-    return Y4_OK;
-}
-
-int y4_conv2d_stem_fwd_f32(const float* x, long long sxb, long long sxc, long long sxh, long long sxw,
-                           const float* w, float* y, int ldy, int B, int H, int W, int Cout,
-                           const float* scale, const float* shift, int act,
-                           float* bnstats_partials, void* stream) {
-    if (!x || !w || !y) return Y4_ERR_NULL;
-    if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cout > 32 || ldy < Cout) return Y4_ERR_SHAPE;
-    StemGeom g{};
-    g.x = x; g.w = w; g.y = y; g.scale = scale; g.shift = shift; g.stats = bnstats_partials;
-    g.sxb = sxb; g.sxc = sxc; g.sxh = sxh; g.sxw = sxw; g.ldy = ldy;
-    g.B = B; g.H = H; g.W = W; g.Cout = Cout; g.act = act;
-    g.M = (long long)B * H * W;
-    const long long blocks = (g.M + 255) / 256;
-    if (blocks >= (1ll << 31)) return Y4_ERR_SHAPE;
-    // matrix-core variant: bf16x3 arithmetic, 32-bit byte offsets into x (non-negative strides)
-    const bool mfma_ok = (g_conv_mode >= 1 && g_conv_mode <= 3) && sxb >= 0 && sxc >= 0 && sxh >= 0 && sxw >= 0 &&
-                         ((long long)(B - 1) * sxb + 2 * sxc + (long long)(H - 1) * sxh + (long long)(W - 1) * sxw + 1) * 4 < 0xfffffff0ll &&
-                         (long long)H * W < (1 << 24);
-    if (mfma_ok) {
-        const int grid = (int)(blocks < 2048 ? blocks : 2048);
-        hipLaunchKernelGGL(conv_stem_fwd_bf16x3_kernel, dim3(grid), dim3(256), 0, y4_stream(stream), g, (int)blocks,
-                           1.0f / (float)((long long)H * W), 1.0f / (float)W);
-        Y4_CHECK_LAUNCH();
-        return Y4_OK;
-    }
-    hipLaunchKernelGGL(conv_stem_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, y4_stream(stream), g);
+        hipLaunchKernelGGL(transpose_filter_kernel, dim3(blocks), dim3(256), 0, st, w, static_cast<float*>(out), Cout, Cin, kk, Cout_pad);
     Y4_CHECK_LAUNCH();
     return Y4_OK;
 }
 
-size_t y4_conv2d_stem_wgrad_workspace(int, int, int, int) {
-    return (size_t)STEM_WAVES * 1024 * sizeof(float) + 64 * 1024 * sizeof(double);
+int igemm_gather(int mode, const ConvGeom& g, bool transposed, hipStream_t st, int* nparts) {
+    return transposed ? dispatch_gather<true>(mode, g, st, nparts) : dispatch_gather<false>(mode, g, st, nparts);
 }
 
-int y4_conv2d_stem_wgrad_f32(const float* x, long long sxb, long long sxc, long long sxh, long long sxw,
-                             const float* dy, int lddy, float* dw, int B, int H, int W, int Cout,
-                             void* workspace, size_t workspace_bytes, void* stream) {
-    if (!x || !dy || !dw || !workspace) return Y4_ERR_NULL;
-    if (B <= 0 || H <= 0 || W < 2 || Cout <= 0 || Cout > 32 || lddy < Cout) return Y4_ERR_SHAPE;
-    if (workspace_bytes < y4_conv2d_stem_wgrad_workspace(B, H, W, Cout)) return Y4_ERR_WORKSPACE;
-    StemWgradGeom g{};
-    g.x = x; g.dy = dy; g.slabs = static_cast<float*>(workspace);
-    g.sxb = sxb; g.sxc = sxc; g.sxh = sxh; g.sxw = sxw; g.lddy = lddy;
-    g.B = B; g.H = H; g.W = W; g.Cout = Cout;
-    g.M = (long long)B * H * W;
-    long long ppw = (g.M + STEM_WAVES - 1) / STEM_WAVES;
-    ppw = (ppw + 15) & ~15ll;                     // 16-pixel trips (8 MFMA pixel pairs) never straddle waves
-    if ((long long)ppw * lddy * 4 >= 0xfffffff0ll || sxb < 0 || sxc < 0 || sxh < 0 || sxw < 0 ||
-        ((long long)(B - 1) * sxb + 2 * sxc + (long long)(H - 1) * sxh + (long long)(W - 1) * sxw + 1) * 4 >= 0xfffffff0ll)
-        return Y4_ERR_SHAPE;
-    g.pix_per_wave = ppw;
-    hipStream_t st = y4_stream(stream);
-    hipLaunchKernelGGL(conv_stem_wgrad_kernel, dim3(STEM_WAVES / 4), dim3(256), 0, st, g);
-    Y4_CHECK_LAUNCH();
-    double* part = reinterpret_cast<double*>(static_cast<char*>(workspace) + (size_t)STEM_WAVES * 1024 * sizeof(float));
-    hipLaunchKernelGGL(stem_wgrad_reduce1_kernel, dim3(64), dim3(256), 0, st, static_cast<const float*>(workspace), part,
-                       STEM_WAVES);
-    Y4_CHECK_LAUNCH();
-    hipLaunchKernelGGL(stem_wgrad_reduce2_kernel, dim3(1), dim3(256), 0, st, part, dw, 64, Cout);
-    Y4_CHECK_LAUNCH();
-    return Y4_OK;
+int igemm_wgrad(int mode, const WgradGeom& g, hipStream_t st) {
+    return mode == 1 ? wgrad_tiles<3>(g, st) : mode == 2 ? wgrad_tiles<1>(g, st) : wgrad_tiles<0>(g, st);
 }
 
-}  // extern "C"
+}  // namespace y4

@@ -1,7 +1,7 @@
 // The 3 -> Cout (<= 32) 3x3 stem in training mode WITHOUT its pre-BatchNorm tensor: y0 = conv(x) is 27 multiply-adds per
 // value out of an input that sits in L1 / L2, while y0 and its gradient dy0 are the two largest tensors of the step
 // (B H W Cout floats each).  Every pass that needs y0 re-forms it in registers with the body of conv_stem_fwd_bf16x3_kernel
-// (conv_igemm.hip) -- the same gather, the same three-piece split, the same 12 MFMAs in the same order, hence the same
+// (conv_stem.hip) -- the same gather, the same three-piece split, the same 12 MFMAs in the same order, hence the same
 // bits in every pass -- and differs only in what it does with the accumulator tile (lane = channel, 16 pixels per lane):
 //   forward   1. statistics   column sums of y0 and y0^2, one row per 256-pixel group (the rows and the order of additions
 //                             of conv_stem_fwd_bf16x3_kernel: bit-identical partials), then y4_bn_finalize_partials_f32
